@@ -1,7 +1,9 @@
 """Train-step throughput of the MI355X-native ScrabbleGAN hot path (BASELINE.json metric:
 train-step images/sec @ 32x160 bs128, 1/2/4/8 GPU; % of the MFMA roofline).
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2                      # the headline figure alone
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full               # + roofline, kernels, configs c3 / c4 / c5, cpu_baseline
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR   # + what the last timed step returned, as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,8 +11,11 @@ A "step" is one full train_step (8 forward passes, 4 backward sweeps, 4 Adam upd
 /root/reference/src/bigacgan/data_utils.py:358-473) on synthetic 32x160 word crops (config c2 of
 SURVEY section 8d: global batch 128, L_r = L_f = 10, fp32), inputs resident in HBM.  The global batch
 is fixed as N grows (strong scaling, gradients SUM-all-reduced over RCCL).  Rank 0 prints ONE JSON
-line; `roofline` is the implicit-GEMM conv kernel (fwd + data-grad launches) timed with HIP events on
-its own stream, `cpu_baseline` is the CPU oracle's train_step on a bounded sample (bs 8).
+line.  A plain run sets up, warms up, times `--steps` steps and prints the headline keys (`value`,
+`ms_per_step`, ...).  Everything that takes runs of its own sits behind `--full`: `roofline` / `kernels` /
+`hbm_kernels` (the conv kernels and the memory-bound families timed with HIP events in extra steps after
+the timed region), `configs` (c3, c4, c5 on freshly built models) and `cpu_baseline` (the CPU oracle's
+train_step on a bounded sample, bs 8).
 """
 from __future__ import annotations
 
@@ -153,11 +158,69 @@ def committed_traffic(kernel, conv_dtype, per_gpu_batch):
 TIMING_IN_REGION = False
 
 
+DUMP_REWIND = 2                     # --dump-outputs: the dumped (last timed) step is this many steps away from the seeded state
+# train_step's return order (data_utils.train permutes it into the columns of data_utils.SUMMARY_HEADER)
+SCALAR_NAMES = ("r_loss_fake", "r_loss_real", "r_loss_balanced", "g_loss", "g_lossT", "g_lossS", "disc_loss", "disc_loss_real",
+                "disc_loss_fake", "g_loss_final", "alpha", "r_loss_fake_std", "g_loss_std", "s_loss", "s_loss_real", "s_loss_fake")
+# r_loss_balanced = alpha * g_loss_std / r_loss_fake_std * r_loss_fake and g_lossS = g_loss + r_loss_balanced are the loss head's
+# fp64 functions of dumped entries; the quotient of the two spreads turns 1e-5 of the logits into 1e-3 of them, so they stay out
+DUMP_DERIVED = ("r_loss_balanced", "g_lossS")
+
+
+class InitialState:
+    """--dump-outputs: the seeded state a run starts from -- weights, BatchNorm moving statistics, Adam slots and step counters,
+    the generators the NonLocalBlock kernels are drawn from -- kept on the device so that the run can be rewound to it.
+    The default step adds through float atomics, and Adam with beta_1 = 0 moves every weight by about +-lr per step
+    whatever the size of its gradient, so the weights of two runs of ONE build separate step by step (measured on MI355X,
+    headline config: after 5 + 20 steps single scalars of the untrained GAN differ by tens of percent) and what a step deep
+    in that trajectory returns is not comparable between runs or builds.  A --dump-outputs run is therefore rewound to the
+    seeded state DUMP_REWIND - 1 steps before its last timed step: the dumped step is step DUMP_REWIND from the seed, its
+    forward passes run on weights that a full step -- every forward, data-grad and weight-grad launch, the gradient exchange
+    and the Adam update of all four networks -- produced.  restore() is queued on the launch stream: device-to-device copies of
+    ~1.6 GB, under 1 ms beside the headline config's 137 ms step, inside the timed region of a --dump-outputs run only."""
+
+    def __init__(self, models, opts):
+        self.pairs = list(zip(models, opts))
+        self.saved = [(m.store.flat.clone(), m.store.state.clone(), m.nl_gen.get_state() if hasattr(m, "nl_gen") else None, o.iterations)
+                      for m, o in self.pairs]
+
+    def restore(self):
+        from scrabble_gan_amd import ops
+        for (m, o), (flat, state, nl_state, iterations) in zip(self.pairs, self.saved):
+            m.store.flat.copy_(flat)
+            m.store.state.copy_(state)
+            for slot in o._slot(m.store.flat):
+                slot.zero_()
+            o.iterations = iterations
+            if nl_state is not None:
+                m.nl_gen.set_state(nl_state)
+        ops.weights_changed()
+
+
+def dump_outputs(path, scalars):
+    """--dump-outputs: what a caller of the timed path receives from its last step: the scalars train_step returns, in its
+    return order (SCALAR_NAMES) without the two DUMP_DERIVED ones (`step_scalars.npy`, float64 [14]; `step_scalars_names.txt`
+    names them, one per line).  A step's scalars are computed from its forward passes; the dumped step is step DUMP_REWIND from
+    the run's seeded state (InitialState), so the file depends on every forward, backward and Adam launch of the step before
+    it and on the forward launches of the dumped step -- not on that step's own backward sweeps and updates, and not on
+    --steps / --warmup where --steps + --warmup >= DUMP_REWIND (a shorter run dumps a step nearer to the seed).  Two runs of
+    one build differ by what float-atomic summation order moves in one step and by the weights whose ~0 gradient lets Adam
+    step them the other way: measured on MI355X, headline config, five runs, <= 1e-4 of max(1, |value|) (1e-9 ... 1e-6 without the
+    rewound update, tens of percent without any rewind)."""
+    os.makedirs(path, exist_ok=True)
+    keep = [i for i, n in enumerate(SCALAR_NAMES) if n not in DUMP_DERIVED]
+    vals = [float(v) for v in scalars]
+    np.save(os.path.join(path, "step_scalars.npy"), np.array([vals[i] for i in keep], np.float64))
+    with open(os.path.join(path, "step_scalars_names.txt"), "w") as f:
+        f.write("\n".join(SCALAR_NAMES[i] for i in keep) + "\n")
+
+
 def measure(conv_dtype, B, L, balance, steps, warmup, timing_steps, reducer, dev, world, bucketed=False, sync_every_step=False,
-            kernel_timing=True, shape_table=None, hbm_families=True, graph=False):
+            kernel_timing=True, shape_table=None, hbm_families=True, graph=False, dump_dir=None):
     """Build the four networks, run `warmup` + `steps` train_steps of one configuration with the inputs resident in HBM, and
     return everything measured: wall time of the timed region (MAX over ranks), HIP-event summaries of the kernel families.
-    The models and every per-step buffer are released before returning."""
+    `dump_dir` (--dump-outputs): the run is rewound to the seeded initial state DUMP_REWIND - 1 steps before the last timed
+    step (InitialState) and what that step returns is written there by rank 0 (dump_outputs).  The models and every per-step buffer are released before returning."""
     from scrabble_gan_amd import data_utils as DU, net_architecture as NA, net_loss, ops, optimizers
     from scrabble_gan_amd.main import build_models
     ops.set_conv_dtype(conv_dtype)
@@ -186,6 +249,7 @@ def measure(conv_dtype, B, L, balance, steps, warmup, timing_steps, reducer, dev
         pair_rng = np.random.default_rng(7)
         pairs = [tuple(int(v) for v in pair_rng.integers(4, 24, 2)) for _ in range(warmup + steps + 2 * timing_steps)]
 
+    initial = InitialState((G, D, R, S), opts) if dump_dir else None      # (opts: generator, discriminator, recognizer, style promoter)
     gs = None
     if graph:       # the step captured once into a HIP graph, then one launch per step (scrabble_gan_amd/graph_step.py)
         from scrabble_gan_amd.graph_step import GraphedStep
@@ -209,7 +273,11 @@ def measure(conv_dtype, B, L, balance, steps, warmup, timing_steps, reducer, dev
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
+    # --dump-outputs: the step before which the run is rewound (a warm-up step where --steps is shorter than the rewind)
+    rewind_at = max(-warmup, steps - DUMP_REWIND) if initial is not None else None
     for i in range(warmup):
+        if rewind_at == i - warmup:
+            initial.restore()
         step(i - warmup)            # negative indices: the warm-up draws its own pairs in --bucketed mode
     # Kernel timing (HIP events around every MFMA conv launch, on the launch stream) runs inside the timed region at
     # N = 1.  At N > 1 the per-GPU batch is small enough for the event records to cost a few percent, so there the
@@ -228,6 +296,8 @@ def measure(conv_dtype, B, L, balance, steps, warmup, timing_steps, reducer, dev
     host_enqueue = 0.0                                            # host time spent queuing the steps (no device waits in there)
     for i in range(steps):
         t_q = time.perf_counter()
+        if rewind_at == i:
+            initial.restore()
         outs.append(step(i))
         host_enqueue += time.perf_counter() - t_q
         if i:
@@ -242,6 +312,9 @@ def measure(conv_dtype, B, L, balance, steps, warmup, timing_steps, reducer, dev
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = t.item()
     assert all(np.isfinite(float(v)) for o in outs for v in o), outs
+    if dump_dir and getattr(reducer, "rank", 0) == 0:
+        dump_outputs(dump_dir, outs[-1])
+    initial = None
     timed_steps = steps
     if timer is not None and not timing_in_region:
         ops.PROFILER = timer
@@ -361,10 +434,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=None, help="GLOBAL batch (fixed as N grows); default 128")
     ap.add_argument("--L", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--timing-in-region", action="store_true", help="HIP-event kernel timing inside the timed region (single stream, N = 1) instead of in extra steps after it")
-    ap.add_argument("--timing-steps", type=int, default=2, help="extra steps after the timed region for the per-kernel HIP-event timing of the memory-bound families (and, at N > 1, of the conv kernels)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure what takes runs of its own: per-kernel HIP-event timing (roofline, kernels, "
+                         "hbm_kernels), the configs c3 / c4 / c5 and the CPU baseline.  Without it the run sets up, warms up, times "
+                         "--steps steps and prints the headline keys")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (its scalars, named in DIR/step_scalars_names.txt) as DIR/step_scalars.npy.  The run is rewound to its "
+                         "seeded initial state one step before that step, so the file depends on one full step (all backward sweeps, "
+                         "all four Adam updates) and the forward passes after it, not on --steps / --warmup, and repeats from run to run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-kernel timing (and the extra configs)")
+    ap.add_argument("--timing-in-region", action="store_true", help="with --full: HIP-event kernel timing inside the timed region (single stream, N = 1) instead of in extra steps after it")
+    ap.add_argument("--timing-steps", type=int, default=2, help="with --full: extra steps after the timed region for the per-kernel HIP-event timing of the memory-bound families (and, at N > 1, of the conv kernels)")
     ap.add_argument("--conv-dtype", default=None, choices=["f32", "bf16", "fp8"],
                     help="matrix-core operand type of the convolutions: f32 = the headline config c2 (default); bf16 = config c3 (run it with --batch 256); "
                          "fp8 = config c5 (fp8 forward / data-grad / weight-grad of the >= 128-channel convs of G/D/S, bf16 recognizer; --batch 512 --balance)")
@@ -372,15 +453,17 @@ def main():
     ap.add_argument("--bucketed", action="store_true",
                     help="config c4: one (L_r, L_f) pair per step drawn U{4..23}^2 from a stream shared by all ranks (bucket_size 23)")
     ap.add_argument("--sync-every-step", action="store_true", help="read the 16 scalars back before queuing the next step")
-    ap.add_argument("--shape-table", default=None, help="write the per-shape time / TFLOP/s table of the MFMA conv kernels here")
+    ap.add_argument("--shape-table", default=None, help="with --full: write the per-shape time / TFLOP/s table of the MFMA conv kernels here")
     ap.add_argument("--no-extra-configs", action="store_true",
-                    help="the default N = 1 invocation also measures configs c3 (bf16, bs 256) and c5 (fp8, bs 512, balancing) after the "
-                         "headline's timed region and reports them under \"configs\"; this flag skips them")
+                    help="the N = 1 invocation with --full and the default config also measures configs c3 (bf16, bs 256), c4 (bucketed, bs 256) "
+                         "and c5 (fp8, bs 512, balancing) after the headline's timed region and reports them under \"configs\"; this flag skips them")
     ap.add_argument("--graph", action="store_true",
                     help="capture the step into a HIP graph once and replay it (single GPU, fixed shapes; no per-kernel timing: the "
                          "roofline object is omitted) -- for the small-batch bf16 / fp8 steps whose host time is within 2x of the GPU time")
     ap.add_argument("--dry-run", action="store_true", help="rendezvous + one all-reduce only, no GPU work (launcher rehearsal on CPU)")
     args = ap.parse_args()
+    if not args.full and (args.shape_table or args.timing_in_region):
+        ap.error("--shape-table / --timing-in-region need the per-kernel timing of --full")
     global TIMING_IN_REGION
     TIMING_IN_REGION = bool(args.timing_in_region)
     plain_invocation = args.conv_dtype is None and args.batch is None and not args.bucketed and not args.balance and args.L == 10 and not args.graph
@@ -414,14 +497,16 @@ def main():
 
     B, L = args.batch, args.L
     res = measure(args.conv_dtype, B, L, args.balance, args.steps, args.warmup, args.timing_steps, reducer, dev, world,
-                  bucketed=args.bucketed, sync_every_step=args.sync_every_step, kernel_timing=not (args.no_kernel_timing or args.graph),
-                  shape_table=args.shape_table if rank == 0 else None, graph=args.graph and world == 1 and not args.bucketed)
+                  bucketed=args.bucketed, sync_every_step=args.sync_every_step,
+                  kernel_timing=args.full and not (args.no_kernel_timing or args.graph),
+                  shape_table=args.shape_table if rank == 0 else None, graph=args.graph and world == 1 and not args.bucketed,
+                  dump_dir=args.dump_outputs)
     res["hbm_steps"] = args.timing_steps
 
-    # configs c3 and c5 of BASELINE.json in the same (driver-run) invocation: after the headline's timed region and its timing
+    # --full: configs c3, c4 and c5 of BASELINE.json in the same invocation: after the headline's timed region and its timing
     # steps, on freshly built models, each with its own warm-up; single GPU only (the scaling runs time c2 alone)
     extra = {}
-    if plain_invocation and world == 1 and not args.no_extra_configs and not args.no_kernel_timing:
+    if args.full and plain_invocation and world == 1 and not args.no_extra_configs and not args.no_kernel_timing:
         for tag, cd, eb, bal in (("c3", "bf16", 256, False), ("c4", "f32", 256, False), ("c5", "fp8", 512, True)):
             try:
                 bk = tag == "c4"            # c4: one (L_r, L_f) pair per step from a shared stream, L in [4, 23] (data_utils.py:62-84,386-392)
@@ -466,7 +551,7 @@ def main():
                                        "multiples of 4, F(2x2,3x3) at 16/36 otherwise (conv_winograd.hip) -- so these rates may exceed the fp32 MFMA peak.  roofline.achieved and kernels.* count the "
                                        "products the matrix cores EXECUTE (Winograd-domain products for those launches) over HIP-event time")
         line["config"]["hip_graph"] = bool(args.graph)
-        line["config"]["streams"] = "S's passes on a second HIP stream beside D's and R's (timed region); per-kernel timing on one stream"
+        line["config"]["streams"] = "S's passes on a second HIP stream beside D's and R's (timed region)" + ("; per-kernel timing on one stream" if args.full else "")
         line["config"]["fused_passes"] = True
         line["config"]["shared_backward"] = True
         line["rccl_ranks"] = torch.distributed.get_world_size() if world > 1 else 1
@@ -482,7 +567,7 @@ def main():
                                           "frac_of_mfma_peak": (fl / (ms * 1e-3) / 1e12 / pk) if pk else None}
         if extra:
             line["configs"] = extra
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if args.full and args.gpus == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline()
             except Exception as e:  # noqa: BLE001

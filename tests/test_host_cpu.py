@@ -193,9 +193,67 @@ def test_cli_entry_points_parse_on_cpu():
         r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, (cmd, r.stderr[-500:])
         assert "usage" in r.stdout.lower()
-    for flag in ("--gpus", "--steps", "--warmup", "--conv-dtype", "--bucketed"):
+    for flag in ("--gpus", "--steps", "--warmup", "--conv-dtype", "--bucketed", "--full", "--dump-outputs"):
         assert flag in subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], cwd=root, capture_output=True,
                                       text=True, timeout=300).stdout
+    # what needs the per-kernel timing is refused without --full instead of being silently dropped
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--shape-table", "t.txt"], cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr
+
+
+def test_bench_dump_restarts_the_last_step_from_the_seeded_state(tmp_path):
+    """bench.py --dump-outputs: InitialState keeps weights, moving statistics, Adam slots / counters and the NonLocalBlock
+    generators of the freshly built networks and puts all of them back IN PLACE (the buffers a captured graph reads keep their
+    addresses); dump_outputs writes the 16 scalars of one step as float64 step_scalars.npy."""
+    import os
+    import sys
+    import types
+    import numpy as np
+    import torch
+    from scrabble_gan_amd import optimizers
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    try:
+        import bench
+    finally:
+        sys.path.remove(root)
+    models, opts = [], []
+    for k in range(2):
+        store = types.SimpleNamespace(flat=torch.linspace(-1.0, 1.0, 37) * (k + 1), state=torch.arange(5.0) + k)
+        m = types.SimpleNamespace(store=store)
+        if k == 0:
+            m.nl_gen = torch.Generator().manual_seed(11)
+        models.append(m)
+        opts.append(optimizers.Adam(2e-4, 0.0, 0.999))
+    first_draw = torch.randn(4, generator=torch.Generator().manual_seed(11))
+    want = [(m.store.flat.clone(), m.store.state.clone()) for m in models]
+    ptrs = [(m.store.flat.data_ptr(), m.store.state.data_ptr()) for m in models]
+    init = bench.InitialState(models, opts)
+    for m, o in zip(models, opts):                  # what a few steps do to the state
+        m.store.flat.add_(0.5)
+        m.store.state.mul_(3.0)
+        for slot in o._slot(m.store.flat):
+            slot.fill_(2.0)
+        o.iterations = 7
+    torch.randn(9, generator=models[0].nl_gen)
+    init.restore()
+    for m, o, (flat, state), (pf, ps) in zip(models, opts, want, ptrs):
+        assert torch.equal(m.store.flat, flat) and torch.equal(m.store.state, state)
+        assert (m.store.flat.data_ptr(), m.store.state.data_ptr()) == (pf, ps)
+        assert o.iterations == 0 and all(float(slot.abs().max()) == 0.0 for slot in o._slot(m.store.flat))
+    assert torch.equal(torch.randn(4, generator=models[0].nl_gen), first_draw)
+    scalars = tuple(float(j) / 3.0 for j in range(15)) + (1,)
+    bench.dump_outputs(str(tmp_path / "d"), scalars)
+    assert sorted(os.listdir(str(tmp_path / "d"))) == ["step_scalars.npy", "step_scalars_names.txt"]
+    got = np.load(str(tmp_path / "d" / "step_scalars.npy"))
+    names = (tmp_path / "d" / "step_scalars_names.txt").read_text().split()
+    # train_step's return order: data_utils.train's permutation of it gives the summary columns
+    from scrabble_gan_amd import data_utils as DU
+    order = (6, 7, 8, 1, 0, 2, 3, 4, 5, 9, 10, 11, 12, 13, 14, 15)
+    assert [bench.SCALAR_NAMES[i] for i in order] == DU.SUMMARY_HEADER.strip().split(";")
+    keep = [i for i in range(16) if bench.SCALAR_NAMES[i] not in ("r_loss_balanced", "g_lossS")]
+    assert keep == [0, 1, 3, 4] + list(range(6, 16)) and names == [bench.SCALAR_NAMES[i] for i in keep]
+    assert got.dtype == np.float64 and np.array_equal(got, np.array([scalars[i] for i in keep], np.float64))
 
 
 def test_pmc_traffic_tool_units_and_gfx950_correction(tmp_path):
