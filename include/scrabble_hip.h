@@ -290,6 +290,28 @@ int sg_attention_bwd(const float* theta, const float* phi, const float* g, const
 int sg_softmax_ctc(const float* logits, const int* labels, int label_stride, float* loss, float* dlogits,
                    int B, int T, int C, int input_length, int label_length, void* stream);
 
+/* ---- reading the recognizer (csrc/ctc_decode.hip; not in the reference, which never decodes R): blank = C-1, C <= 64.
+ * All pointers are caller-owned device pointers, nothing is allocated, work is asynchronous on `stream`;
+ * returns 0, SG_ERR_ARG or SG_ERR_UNSUPPORTED (SG_ERR_LAUNCH if the launch itself failed). */
+/* lp [B,T,C] = log_softmax(log(softmax(logits) + 1e-7)): the per-frame log-probabilities sg_softmax_ctc scores with */
+int sg_ctc_log_probs(const float* logits, float* lp, int B, int T, int C, void* stream);
+/* best path over frames t < input_length: argmax per frame (a tie takes the lowest class), equal neighbours merged, blanks
+ * dropped.  out_labels int32 [B,out_stride]: the characters in [:out_len[b]], -1 behind them; out_stride >= input_length.
+ * out_logp [B] (nullable) = sum over the used frames of the winning class's lp */
+int sg_ctc_greedy_decode(const float* logits, int* out_labels, int* out_len, float* out_logp, int B, int T, int C,
+                         int input_length, int out_stride, void* stream);
+/* nll [B,W] = CTC negative log-likelihood of word w (words int32 [W,word_stride], word_len int32 [W]) on sample b, from the lp
+ * of sg_ctc_log_probs.  +inf for a word that needs more than input_length frames, for word_len outside
+ * [1, min(word_stride, 31)] and for a label outside [0, C-2].  input_length * C * 4 bytes <= 64 KiB, B <= 65535 */
+int sg_ctc_score_words(const float* lp, const int* words, const int* word_len, int word_stride, float* nll, int B, int T, int C,
+                       int input_length, int W, void* stream);
+/* dist int32 [B] = Levenshtein distance (unit costs) of hyp[b,:hyp_len[b]] and ref[b,:ref_len[b]]; lengths may be 0.
+ * ref_stride <= 63 (SG_ERR_UNSUPPORTED beyond); a length that is negative or exceeds its stride gives dist[b] = -1 */
+int sg_edit_distance(const int* hyp, const int* hyp_len, int hyp_stride, const int* ref, const int* ref_len, int ref_stride,
+                     int* dist, int B, void* stream);
+/* sums fp64 [4] += {sum dist, sum ref_len, #(dist != 0), B}: additive over batches and ranks, the caller zeroes it once */
+int sg_legibility_sums(const int* dist, const int* ref_len, int B, double* sums, void* stream);
+
 /* ---- losses + gradient balancing + statistics (net_loss.py:4-54; data_utils.py:418-442,476-490) */
 /* mode 0 hinge, 1 not_saturating.  sums: fp64 [12] (all-reduce across ranks between the two calls) */
 int sg_loss_sums(const float* d_r, const float* d_f, const float* s_my, const float* s_f, const float* s_r, const float* r_f,

@@ -426,11 +426,16 @@ SUMMARY_HEADER = ("disc_loss;disc_loss_real;disc_loss_fake;r_loss_real;r_loss_fa
 def train(dataset, generator, discriminator, recognizer, style_promoter, composite_gan, checkpoint, checkpoint_prefix,
           generator_optimizer, discriminator_optimizer, recognizer_optimizer, stylepromoter_optimizer, my_imgs,
           seed_labels, buffer_size, batch_size, epochs, model_path, latent_dim, gen_path, loss_fn, disc_iters,
-          apply_gradient_balance, random_words, bucket_size, char_vector, max_batches_per_epoch=None, state_path=None):
+          apply_gradient_balance, random_words, bucket_size, char_vector, max_batches_per_epoch=None, state_path=None,
+          legibility_every=0):
     """Epoch/batch loop, 16-column ';' summaries and per-epoch G/R weight saves (data_utils.py:198-352).
     The summary rows carry the ';' the reference drops between g_loss_std and s_loss (Appendix C-10).
     `state_path` (not in the reference): full training state written there after every epoch and, when the file exists
-    at start, loaded first -- training continues with the epoch after the saved one."""
+    at start, loaded first -- training continues with the epoch after the saved one.
+    `legibility_every` = N > 0 (not in the reference): after every Nth epoch one line `epoch,n,cer_real,wer_real,cer_fake,wer_fake`
+    is appended to <model_path>/legibility.csv -- R's best-path reading (legibility.py) of the epoch's last real batch and of G's
+    inference rendering of that step's fake labels.  The step's host draws are the same with and without it, and the
+    evaluation puts back the state of every generator it touches; 0 (default) changes nothing."""
     generator_save_dir = os.path.join(checkpoint_prefix, 'generator/')
     recognizer_save_dir = os.path.join(checkpoint_prefix, 'recognizer/')
     # data parallel: every rank runs the loop (same seeded host streams -> same batches, each rank takes its slice inside
@@ -463,6 +468,7 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
         for epoch_idx in range(first_epoch, epochs):
             start = time.time()
             totals = [0.0] * 16
+            fake_labels = None
             pending = None          # the previous step's scalars: read back after the next step is queued, so the
                                     # device-to-host copy of the 16 values never drains the launch queue
             def flush(res):
@@ -472,10 +478,17 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
             for batch_idx in range(batch_per_epoch):
                 image_batch, label_batch = next(dataset)
                 my_img_batch = random.choices(my_imgs, k=batch_size)
+                fake_labels = None
+                if legibility_every > 0 and (epoch_idx + 1) % legibility_every == 0 and batch_idx == batch_per_epoch - 1:
+                    # the evaluation below needs this step's fake labels: train_step's own draw (and rank-0 broadcast), made here
+                    _, fake_labels = draw_fake_labels(random_words, bucket_size, batch_size)
+                    if generator.reducer.world_size > 1:
+                        fake_labels = generator.reducer.broadcast_object(fake_labels)
                 out = train_step(epoch_idx, batch_idx, batch_per_epoch, image_batch, label_batch, discriminator, recognizer,
                                  style_promoter, composite_gan, generator_optimizer, discriminator_optimizer,
                                  recognizer_optimizer, stylepromoter_optimizer, my_img_batch, batch_size, latent_dim, loss_fn,
-                                 disc_iters, apply_gradient_balance, random_words, bucket_size, gen_path, sync="lazy")
+                                 disc_iters, apply_gradient_balance, random_words, bucket_size, gen_path, sync="lazy",
+                                 fake_labels=fake_labels)
                 if pending is not None:
                     flush(pending)
                 pending = out
@@ -485,6 +498,19 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
             print('Time for epoch {} is {} sec'.format(epoch_idx + 1, time.time() - start))
             if not is_main:
                 continue
+            if fake_labels is not None:
+                from .legibility import LEGIBILITY_HEADER, epoch_legibility
+                style = (torch.stack(list(my_img_batch), 0) if torch.is_tensor(my_img_batch[0])
+                         else np.stack([np.asarray(m) for m in my_img_batch], 0))
+                leg = epoch_legibility(generator, recognizer, image_batch, label_batch, style, fake_labels)
+                os.makedirs(model_path, exist_ok=True)
+                leg_path = os.path.join(model_path, "legibility.csv")
+                new = not os.path.exists(leg_path)
+                with open(leg_path, "a") as f:
+                    if new:
+                        f.write(LEGIBILITY_HEADER)
+                    f.write(",".join(str(v) for v in (epoch_idx + 1, leg["n"], leg["cer_real"], leg["wer_real"], leg["cer_fake"],
+                                                      leg["wer_fake"])) + "\n")
             generator.save_weights(os.path.join(generator_save_dir, str(epoch_idx + 1), 'cktp-' + str(epoch_idx + 1)))
             recognizer.save_weights(os.path.join(recognizer_save_dir, str(epoch_idx + 1), 'cktp-' + str(epoch_idx + 1)))
             if state_path is not None:

@@ -92,6 +92,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0, help="seed of the host RNG streams (random, numpy) and of the weight initialisers")
     ap.add_argument("--deterministic", action="store_true",
                     help="no float-atomic reduction splits in the conv kernels: bitwise reproducible runs, a few percent slower")
+    ap.add_argument("--legibility-every", type=int, default=0,
+                    help="after every Nth epoch append R's character / word error rates on real and generated words to <model_dir>/legibility.csv")
     args = ap.parse_args(argv)
 
     # Data parallel (one process per GPU under torch.distributed.run): join the job BEFORE any GPU work, give every rank the
@@ -135,7 +137,8 @@ def main(argv=None):
           discriminator_optimizer, recognizer_optimizer, stylepromoter_optimizer, train_imgs, [None, labels], buf_size, batch_size,
           epochs, m_path, latent_dim, gen_path, loss_fn, disc_iters, apply_gradient_balance, random_words, bucket_size, char_vec,
           max_batches_per_epoch=args.steps,
-          state_path=os.path.join(ckpt_path, "state", "latest.safetensors") if args.resumable else None)
+          state_path=os.path.join(ckpt_path, "state", "latest.safetensors") if args.resumable else None,
+          legibility_every=args.legibility_every)
 
 
 if __name__ == "__main__":

@@ -502,10 +502,16 @@ class RecognizerModel(_Model):
             return self._forward(x, labels, input_length, label_length, training, need_grad)
 
     def _forward(self, x, labels, input_length, label_length, training=True, need_grad=True):
-        p = self.store.p
-        x = _as_nhwc1(x, self.device)
         labels = _as_labels(labels, self.device)
         bn_training = bool(training and self.trainable)        # TF2: training AND layer.trainable (fact 4)
+        logits, acts, feat, (B, T) = self._trunk(x, bn_training)
+        loss, dlogits = ops.softmax_ctc(logits, labels, int(input_length), int(label_length), need_grad)
+        return loss, (acts, feat, dlogits, (B, T))
+
+    def _trunk(self, x, bn_training):
+        """Conv stack + Dense -> pre-softmax logits [B,T,classes] and what the backward sweep needs."""
+        p = self.store.p
+        x = _as_nhwc1(x, self.device)
         acts, net = [], x
         for i, (k, co, pool) in enumerate(_REC):
             a = ops.conv2d_fwd(net, p["conv%d.w" % (i + 1)], p["conv%d.b" % (i + 1)], same=(k == 3), relu_out=True)
@@ -519,9 +525,34 @@ class RecognizerModel(_Model):
         B, one, T, C = net.shape
         assert one == 1, net.shape
         feat = net.view(B * T, C)
-        logits = ops.dense_fwd(feat, p["dense.w"], p["dense.b"]).view(B, T, self.classes)     # Dense (softmax fused below)
-        loss, dlogits = ops.softmax_ctc(logits, labels, int(input_length), int(label_length), need_grad)
-        return loss, (acts, feat, dlogits, (B, T))
+        logits = ops.dense_fwd(feat, p["dense.w"], p["dense.b"]).view(B, T, self.classes)     # Dense (softmax fused into the CTC head)
+        return logits, acts, feat, (B, T)
+
+    # ---- reading the recognizer (not in the reference: its R only ever returns the CTC cost) ----
+    def logits(self, x, training=False):
+        """Pre-softmax Dense output [B,T,classes] of the forward pass, without labels or CTC.  With the default
+        training=False BatchNorm uses its moving statistics and nothing in the model changes."""
+        with ops.bf16_only():
+            return self._trunk(x, bool(training and self.trainable))[0]
+
+    def transcribe(self, x, input_length=None):
+        """Best-path reading of the first `input_length` frames (default: the 4L-1 the CTC head trains on) -> (labels int32 [B,input_length] with -1
+        behind each word, lengths int32 [B], logp [B] = log-probability of the best path)."""
+        logits = self.logits(x)
+        return ops.ctc_greedy_decode(logits, self._ctc_frames(logits.shape[1]) if input_length is None else input_length)
+
+    def score_words(self, x, words, word_len, input_length=None):
+        """CTC negative log-likelihood [B,W] of every candidate word (int32 [W,stride] rows, int32 [W] lengths) on every
+        image: the cost __call__ returns, for W words of mixed lengths from one forward pass."""
+        words, word_len = _as_labels(words, self.device), _as_labels(word_len, self.device)
+        logits = self.logits(x)
+        return ops.ctc_score_words(ops.ctc_log_probs(logits), words, word_len,
+                                   self._ctc_frames(logits.shape[1]) if input_length is None else input_length)
+
+    @staticmethod
+    def _ctc_frames(T):
+        """Frames the CTC head reads when the caller names none: all T = 4L-1 of them."""
+        return T
 
     def can_merge(self, training=True) -> bool:
         """Calls may share one pass only while BatchNorm is in inference mode (per-sample independent)."""
@@ -708,12 +739,28 @@ class MyRecognizerModel(RecognizerModel):
         return m
 
     def forward(self, x, labels, input_length, label_length, training=True, need_grad=True, masks=None):
-        p, S = self.store.p, self.store
         x = _as_nhwc1(x, self.device)
         labels = _as_labels(labels, self.device)
         bn_training = bool(training and self.trainable)        # TF2: training AND layer.trainable
         if training and masks is None:
             masks = self.draw_masks(x.shape[0], x.shape[2])      # Keras Dropout follows `training` only
+        logits, acts, lstm_ctx, feat, (B, T) = self._trunk(x, bn_training, masks)
+        loss, dlogits = ops.softmax_ctc(logits, labels, int(input_length), int(label_length), need_grad)
+        return loss, (acts, lstm_ctx, feat, dlogits, masks, (B, T))
+
+    def logits(self, x, training=False):
+        """Pre-softmax Dense output [B,T,classes], T = W/4.  training=False: moving statistics, no dropout masks."""
+        x = _as_nhwc1(x, self.device)
+        masks = self.draw_masks(x.shape[0], x.shape[2]) if training else None
+        return self._trunk(x, bool(training and self.trainable), masks)[0]
+
+    @staticmethod
+    def _ctc_frames(T):
+        """This model emits T = 4L frames and its CTC head reads the first 4L-1 (data_utils.ctc_input_length)."""
+        return max(T - 1, 1)
+
+    def _trunk(self, x, bn_training, masks=None):
+        p, S = self.store.p, self.store
         acts, net = [], x
         for i, (co, pool) in enumerate(zip(_MYREC_FILTERS, _MYREC_POOLS)):
             k = i + 1
@@ -739,8 +786,7 @@ class MyRecognizerModel(RecognizerModel):
             seq = ops.mul_mask(seq, masks["drop_out"])
         feat = seq.reshape(B * T, seq.shape[2])
         logits = ops.dense_fwd(feat, p["dense.w"], p["dense.b"]).view(B, T, self.classes)
-        loss, dlogits = ops.softmax_ctc(logits, labels, int(input_length), int(label_length), need_grad)
-        return loss, (acts, lstm_ctx, feat, dlogits, masks, (B, T))
+        return logits, acts, lstm_ctx, feat, (B, T)
 
     def backward(self, ctx, upstream, want_dx: bool, want_dw: bool):
         p, g, S = self.store.p, self.store.g, self.store

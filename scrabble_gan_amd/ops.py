@@ -1491,6 +1491,80 @@ def softmax_ctc(logits, labels, input_length, label_length, need_grad=True):
     return loss, dlogits
 
 
+# ---------------------------------------------------------------- reading the recognizer (csrc/ctc_decode.hip)
+def _chk_i32(*ts):
+    for t in ts:
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32):
+            raise ValueError("expected a contiguous int32 CUDA tensor, got %s %s contiguous=%s" % (t.device, t.dtype, t.is_contiguous()))
+
+
+def ctc_log_probs(logits):
+    """[B,T,C] logits -> lp = log_softmax(log(softmax(logits) + 1e-7)), the per-frame log-probabilities softmax_ctc scores with."""
+    _chk(logits)
+    B, T, C = logits.shape
+    lp = torch.empty_like(logits)
+    call("sg_ctc_log_probs", _p(logits), _p(lp), B, T, C, _stream())
+    return lp
+
+
+def ctc_greedy_decode(logits, input_length=None, want_logp=True):
+    """Best-path decoding of the frames t < input_length -> (labels int32 [B,input_length] with -1 behind the word,
+    lengths int32 [B], logp [B] or None)."""
+    _chk(logits)
+    B, T, C = logits.shape
+    input_length = T if input_length is None else int(input_length)
+    if not (0 < input_length <= T):
+        raise ValueError("CTC input_length %d out of range (T = %d)" % (input_length, T))
+    labels = empty(B, input_length, like=logits, dtype=torch.int32)
+    lengths = empty(B, like=logits, dtype=torch.int32)
+    logp = empty(B, like=logits) if want_logp else None
+    call("sg_ctc_greedy_decode", _p(logits), labels.data_ptr(), lengths.data_ptr(), _p(logp), B, T, C, input_length, input_length, _stream())
+    return labels, lengths, logp
+
+
+def ctc_score_words(lp, words, word_len, input_length=None):
+    """lp [B,T,C] (ctc_log_probs), words int32 [W,stride], word_len int32 [W] -> CTC negative log-likelihood [B,W]
+    (+inf: infeasible word, length outside [1, min(stride, 31)], label outside [0, C-2])."""
+    _chk(lp)
+    _chk_i32(words, word_len)
+    B, T, C = lp.shape
+    input_length = T if input_length is None else int(input_length)
+    if not (0 < input_length <= T):
+        raise ValueError("CTC input_length %d out of range (T = %d)" % (input_length, T))
+    if words.dim() != 2 or words.shape[1] < 1 or word_len.shape != (words.shape[0],) or words.shape[0] < 1:
+        raise ValueError("words %s / word_len %s: expected [W,stride] and [W], W >= 1" % (tuple(words.shape), tuple(word_len.shape)))
+    W = words.shape[0]
+    nll = empty(B, W, like=lp)
+    call("sg_ctc_score_words", _p(lp), words.data_ptr(), word_len.data_ptr(), words.shape[1], _p(nll), B, T, C, input_length, W, _stream())
+    return nll
+
+
+def edit_distance(hyp, hyp_len, ref, ref_len):
+    """Levenshtein distance int32 [B] of hyp[b,:hyp_len[b]] and ref[b,:ref_len[b]] (int32 rows; ref at most 63 wide)."""
+    _chk_i32(hyp, hyp_len, ref, ref_len)
+    B = hyp.shape[0]
+    if hyp.dim() != 2 or ref.dim() != 2 or ref.shape[0] != B or hyp_len.shape != (B,) or ref_len.shape != (B,):
+        raise ValueError("edit_distance: hyp %s, hyp_len %s, ref %s, ref_len %s" % (tuple(hyp.shape), tuple(hyp_len.shape), tuple(ref.shape),
+                                                                                     tuple(ref_len.shape)))
+    dist = torch.empty(B, device=hyp.device, dtype=torch.int32)
+    call("sg_edit_distance", hyp.data_ptr(), hyp_len.data_ptr(), hyp.shape[1], ref.data_ptr(), ref_len.data_ptr(), ref.shape[1],
+         dist.data_ptr(), B, _stream())
+    return dist
+
+
+def legibility_sums(dist, ref_len, sums=None):
+    """sums fp64 [4] += {sum dist, sum ref_len, #(dist != 0), B}; a zeroed buffer is made when none is given."""
+    _chk_i32(dist, ref_len)
+    if dist.shape != ref_len.shape or dist.dim() != 1:
+        raise ValueError("legibility_sums: dist %s, ref_len %s" % (tuple(dist.shape), tuple(ref_len.shape)))
+    if sums is None:
+        sums = torch.zeros(4, device=dist.device, dtype=torch.float64)
+    elif not (sums.is_cuda and sums.is_contiguous() and sums.dtype == torch.float64 and sums.numel() == 4):
+        raise ValueError("legibility_sums: sums must be a contiguous fp64 CUDA tensor of 4 elements")
+    call("sg_legibility_sums", dist.data_ptr(), ref_len.data_ptr(), dist.numel(), sums.data_ptr(), _stream())
+    return sums
+
+
 # ---------------------------------------------------------------- loss head
 def loss_sums(d_r, d_f, s_my, s_f, s_r, r_f, r_r, mode: int):
     _chk(d_r, d_f, s_my, s_f, s_r, r_f, r_r)

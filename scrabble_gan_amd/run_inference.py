@@ -3,11 +3,13 @@
 `generator([style_imgs, labels], training=False)`).
 
     python -m scrabble_gan_amd.run_inference --weights run/checkpoints/generator/15/cktp-15 --words machinelearning \
-        [--style-dir DIR | --synthetic-style] [--count 10] --out words.png
+        [--style-dir DIR | --synthetic-style] [--count 10] --out words.png [--read-back --recognizer-weights PREFIX [--my-rec]]
 
 The checkpoint is the `<prefix>.safetensors` file `train()` writes per epoch (`_Model.save_weights`).  BatchNorm runs in
 inference mode (moving statistics).  The output PNG stacks the `count` renderings of each word vertically (the
-reference shows them as a 10 x 1 matplotlib grid) after the reference's (x + 1) / 2 mapping to [0, 1]."""
+reference shows them as a 10 x 1 matplotlib grid) after the reference's (x + 1) / 2 mapping to [0, 1].
+`--read-back` (not in the reference) also has a trained recognizer read each word's first rendering and prints one line per
+word: target, what R read, edit distance (legibility.read_back)."""
 from __future__ import annotations
 
 import argparse
@@ -58,7 +60,12 @@ def main(argv=None):
     ap.add_argument("--count", type=int, default=10, help="renderings per word (= style images used)")
     ap.add_argument("--out", default="generated.png")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--read-back", action="store_true", help="print what the recognizer reads from each generated word")
+    ap.add_argument("--recognizer-weights", default=None, help="recognizer checkpoint prefix (with --read-back)")
+    ap.add_argument("--my-rec", action="store_true", help="the recognizer checkpoint is the BiLSTM model's")
     args = ap.parse_args(argv)
+    if args.read_back and not args.recognizer_weights:
+        ap.error("--read-back needs --recognizer-weights PREFIX")
 
     from . import net_architecture as NA
     NA.configure(device=torch.device(args.device))
@@ -81,6 +88,12 @@ def main(argv=None):
         rows += [np.pad(i, ((0, 0), (0, widest - i.shape[1]), (0, 0)), constant_values=1.0) for i in imgs]
     save_grid(np.stack(rows), args.out)
     print("wrote %s: %d rows (%d words x %d styles)" % (args.out, len(rows), len(args.words), len(style)))
+    if args.read_back:
+        from .legibility import read_back
+        R = (NA.make_my_recognizer if args.my_rec else NA.make_recognizer)(in_dim, None, len(CHAR_VEC) + 1, vis_model=False)
+        R.load_weights(args.recognizer_weights)
+        for r in read_back(G, R, style[:1], args.words, CHAR_VEC):
+            print("%s\t%s\t%d" % (r["target"], r["read"], r["distance"]))
 
 
 if __name__ == "__main__":
