@@ -361,6 +361,20 @@ int sg_spectral_norm_bwd(const float* w, const float* u, const float* g, float* 
 int sg_normalize_u8(const unsigned char* u8, float* out, long n, void* stream);
 int sg_bias_add(float* y, const float* bias, long M, int C, void* stream);
 
+/* ---- averaged generator (scrabble_gan_amd/averaging.py; csrc/averaging.hip) ---------------------------------------------
+ * sg_ema_update: ema[i] += one_minus_decay * (p[i] - ema[i]) over a flat buffer, one sweep (12 B per weight).  The caller
+ * computes 1 - decay in double and rounds once (1 - 0.9999f in fp32 loses half its digits).  one_minus_decay == 0 launches
+ * nothing (ema bitwise unchanged), == 1 copies p (ema bitwise equal to p).  SG_ERR_ARG before any launch: a base pointer that
+ * is not 16-byte aligned, n < 0, one_minus_decay outside [0, 1].
+ * sg_swap_f32: a <-> b in place (same alignment rule; the buffers are disjoint or the same one).
+ * sg_image_sheet_u8: imgs [N,H,W,1] in [-1,1] laid out row-major on a uint8 sheet of ceil(N/cols) x cols cells,
+ * [rows*(H+pad)-pad, cols*(W+pad)-pad]; pixel = round(clip((x + 1) / 2, 0, 1) * 255) in fp32, that order, round-half-even
+ * (byte-identical to the numpy expression of run_inference.save_grid); gutters and unused cells = fill (0..255).  The inverse
+ * direction of sg_normalize_u8.  sheet is 4-byte aligned. */
+int sg_ema_update(float* ema, const float* p, long n, float one_minus_decay, void* stream);
+int sg_swap_f32(float* a, float* b, long n, void* stream);
+int sg_image_sheet_u8(const float* imgs, unsigned char* sheet, int N, int H, int W, int cols, int pad, int fill, void* stream);
+
 /* ---- collective of the data-parallel step (the reference has none: BASELINE.json north_star) ----------
  * SUM all-reduce, in place, of `n` elements of a flat device buffer over RCCL on `stream`; gradients are sums over the
  * batch (reference data_utils.py:450,454,458,467 differentiate [B,1] targets), so ranks ADD.  comm = the ncclComm_t made by

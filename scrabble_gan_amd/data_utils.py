@@ -387,8 +387,46 @@ class StepScalars:
 # Full training state: the reference saves G and R weights per epoch and cannot resume; this
 # writes EVERYTHING a restart needs -- parameters and BN moving statistics of all four networks, the optimizer slots and
 # step counters -- into one safetensors file (no pickle), plus the epoch / batch position.
+_GEN_ATTRS = ("nl_gen", "sn_gen", "mask_gen")
+
+
+def _stream_states(models) -> dict:
+    """The random streams a run draws from between two epochs, as tensors: Python's `random`, numpy's global generator and the
+    generators the models own (NonLocalBlock kernels, spectral-norm vectors, dropout masks)."""
+    _, mt, gauss = random.getstate()
+    out = {"rng/random": torch.tensor(mt, dtype=torch.int64),
+           "rng/random.gauss": torch.tensor([float("nan") if gauss is None else gauss], dtype=torch.float64)}
+    _, keys, pos, has_gauss, cached = np.random.get_state()
+    out["rng/numpy"] = torch.tensor([int(k) for k in keys] + [int(pos), int(has_gauss)], dtype=torch.int64)
+    out["rng/numpy.gauss"] = torch.tensor([float(cached)], dtype=torch.float64)
+    for tag, m in models:
+        for a in _GEN_ATTRS:
+            if hasattr(m, a):
+                out["rng/%s.%s" % (tag, a)] = getattr(m, a).get_state().clone()
+    return out
+
+
+def _restore_streams(st, models) -> bool:
+    if "rng/random" not in st:
+        return False
+    gauss = st["rng/random.gauss"].item()
+    random.setstate((3, tuple(st["rng/random"].tolist()), None if gauss != gauss else gauss))
+    v = st["rng/numpy"].tolist()
+    np.random.set_state(("MT19937", np.array(v[:624], np.uint32), v[624], v[625], st["rng/numpy.gauss"].item()))
+    for tag, m in models:
+        for a in _GEN_ATTRS:
+            k = "rng/%s.%s" % (tag, a)
+            if hasattr(m, a) and k in st:
+                getattr(m, a).set_state(st[k])
+    return True
+
+
 def save_training_state(path, generator, discriminator, recognizer, style_promoter, generator_optimizer, discriminator_optimizer,
-                        recognizer_optimizer, stylepromoter_optimizer, epoch_idx=0, batch_idx=0):
+                        recognizer_optimizer, stylepromoter_optimizer, epoch_idx=0, batch_idx=0, averages=None, streams=False):
+    """`averages` (optional): {"G": averaging.WeightAverage} -- its buffer, update counter and standing statistics are stored under
+    `G.ema/...`.  `streams=True` also stores the random streams of the run (`rng/...`: `random`, numpy, the models' generators): an
+    average is a function of the whole trajectory, so a resumed run continues it exactly only if it draws what the uninterrupted run
+    would have drawn.  Without either the file has the keys it always had."""
     from safetensors.torch import save_file
     out = {"position": torch.tensor([int(epoch_idx), int(batch_idx)], dtype=torch.int64)}
     for tag, m, opt in (("G", generator, generator_optimizer), ("D", discriminator, discriminator_optimizer),
@@ -397,6 +435,11 @@ def save_training_state(path, generator, discriminator, recognizer, style_promot
             out["%s/%s" % (tag, k)] = v.contiguous()
         for k, v in opt.flat_state(m.store).items():
             out["%s.opt/%s" % (tag, k)] = v.detach().cpu().contiguous()
+    for tag, avg in (averages or {}).items():
+        for k, v in avg.state_dict().items():
+            out["%s.ema/%s" % (tag, k)] = v.contiguous()
+    if streams:
+        out.update(_stream_states((("G", generator), ("D", discriminator), ("R", recognizer), ("S", style_promoter))))
     d = os.path.dirname(path)
     if d:
         os.makedirs(d, exist_ok=True)
@@ -405,8 +448,10 @@ def save_training_state(path, generator, discriminator, recognizer, style_promot
 
 
 def load_training_state(path, generator, discriminator, recognizer, style_promoter, generator_optimizer, discriminator_optimizer,
-                        recognizer_optimizer, stylepromoter_optimizer):
-    """Restores what save_training_state wrote; -> (epoch_idx, batch_idx) of the save."""
+                        recognizer_optimizer, stylepromoter_optimizer, averages=None, streams=False):
+    """Restores what save_training_state wrote; -> (epoch_idx, batch_idx) of the save.  `averages` = {"G": WeightAverage}: restored from
+    the `G.ema/...` tensors; with a state written without them the average restarts as a copy of the loaded weights.
+    `streams=True` puts the saved random streams (`rng/...`) back when the file has them."""
     from safetensors.torch import load_file
     st = load_file(path)
     for tag, m, opt in (("G", generator, generator_optimizer), ("D", discriminator, discriminator_optimizer),
@@ -414,6 +459,15 @@ def load_training_state(path, generator, discriminator, recognizer, style_promot
         pre, opre = tag + "/", tag + ".opt/"
         m.store.load({k[len(pre):]: v for k, v in st.items() if k.startswith(pre)})
         opt.load_flat_state(m.store, {k[len(opre):]: v for k, v in st.items() if k.startswith(opre)})
+    for tag, avg in (averages or {}).items():
+        epre = tag + ".ema/"
+        sd = {k[len(epre):]: v for k, v in st.items() if k.startswith(epre)}
+        if sd:
+            avg.load_state_dict(sd)
+        else:                                             # a state from a run without averaging: the average starts at the loaded weights
+            avg.flat.copy_(avg.model.store.flat)
+    if streams:                                           # (a state written without them: the streams stay where they are)
+        _restore_streams(st, (("G", generator), ("D", discriminator), ("R", recognizer), ("S", style_promoter)))
     ops.weights_changed()
     pos = st["position"].tolist()
     return int(pos[0]), int(pos[1])
@@ -427,7 +481,7 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
           generator_optimizer, discriminator_optimizer, recognizer_optimizer, stylepromoter_optimizer, my_imgs,
           seed_labels, buffer_size, batch_size, epochs, model_path, latent_dim, gen_path, loss_fn, disc_iters,
           apply_gradient_balance, random_words, bucket_size, char_vector, max_batches_per_epoch=None, state_path=None,
-          legibility_every=0):
+          ema_decay=0.0, ema_start=0, ema_standing_batches=0, samples_every=0, legibility_every=0):
     """Epoch/batch loop, 16-column ';' summaries and per-epoch G/R weight saves (data_utils.py:198-352).
     The summary rows carry the ';' the reference drops between g_loss_std and s_loss (Appendix C-10).
     `state_path` (not in the reference): full training state written there after every epoch and, when the file exists
@@ -435,7 +489,19 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
     `legibility_every` = N > 0 (not in the reference): after every Nth epoch one line `epoch,n,cer_real,wer_real,cer_fake,wer_fake`
     is appended to <model_path>/legibility.csv -- R's best-path reading (legibility.py) of the epoch's last real batch and of G's
     inference rendering of that step's fake labels.  The step's host draws are the same with and without it, and the
-    evaluation puts back the state of every generator it touches; 0 (default) changes nothing."""
+    evaluation puts back the state of every generator it touches; 0 (default) changes nothing.
+    `ema_decay` > 0 (not in the reference): every rank keeps an exponential moving average of G's weights (averaging.WeightAverage,
+    decay warm-up on, the plain copy of the weights for the first `ema_start` steps), updated by one sweep after each step -- it never
+    feeds back into training.  Per epoch rank 0 writes it to <checkpoints>/generator_ema/<e>/cktp-<e> (the layout of generator/, so
+    `load_weights`, run_inference and evaluate take it); its BatchNorm statistics are re-estimated over `ema_standing_batches`
+    training-mode batches of random style images and fake words when that is > 0 (drawn without advancing `random`), else copied from
+    the live generator.  With `legibility_every`, legibility_ema.csv holds the same columns with cer_fake / wer_fake read from the
+    averaged generator.  The full state (`state_path`) then also carries the average and the run's random streams, and a resumed run
+    skips the batches of the finished epochs, so it continues the average exactly.
+    `samples_every` = N > 0: after every Nth epoch <gen_path>/image_at_epoch_NNNN.png (the reference's per-epoch picture,
+    data_utils.py:493-519) shows the words `seed_labels[1]` in the styles of the first len(words) entries of `my_imgs`, rendered by the
+    averaged generator when there is one, else by G.  With all four at their defaults nothing is launched, drawn or written that
+    was not before."""
     generator_save_dir = os.path.join(checkpoint_prefix, 'generator/')
     recognizer_save_dir = os.path.join(checkpoint_prefix, 'recognizer/')
     # data parallel: every rank runs the loop (same seeded host streams -> same batches, each rank takes its slice inside
@@ -454,9 +520,23 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
     print('epoch size:           ', epochs)
     order = (6, 7, 8, 1, 0, 2, 3, 4, 5, 9, 10, 11, 12, 13, 14, 15)      # return tuple -> summary column order
     first_epoch = 0
+    avg = None
+    if ema_decay > 0:
+        from .averaging import WeightAverage
+        avg = WeightAverage(generator, decay=ema_decay, start_step=ema_start)
+    averages = {"G": avg} if avg is not None else None
     if state_path is not None and os.path.exists(state_path):
+        if avg is not None:
+            # the dataset's position is not part of the state: the batches of the finished epochs are drawn and dropped (before the
+            # saved streams are put back), so the resumed run sees what the uninterrupted one would
+            from safetensors import safe_open
+            with safe_open(state_path, framework="pt") as f:
+                done = int(f.get_tensor("position")[0]) + 1
+            for _ in range(done * batch_per_epoch):
+                next(dataset)
         saved_epoch, _ = load_training_state(state_path, generator, discriminator, recognizer, style_promoter, generator_optimizer,
-                                             discriminator_optimizer, recognizer_optimizer, stylepromoter_optimizer)
+                                             discriminator_optimizer, recognizer_optimizer, stylepromoter_optimizer,
+                                             averages=averages, streams=avg is not None)
         first_epoch = saved_epoch + 1
         print('resumed from %s: continuing with epoch %d' % (state_path, first_epoch + 1))
     mode = "a" if first_epoch > 0 else "w"                   # a resumed run appends to the summaries of the first one
@@ -489,6 +569,8 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
                                  recognizer_optimizer, stylepromoter_optimizer, my_img_batch, batch_size, latent_dim, loss_fn,
                                  disc_iters, apply_gradient_balance, random_words, bucket_size, gen_path, sync="lazy",
                                  fake_labels=fake_labels)
+                if avg is not None:
+                    avg.update()                             # outside the step (and outside a captured one): one sweep over G's buffer
                 if pending is not None:
                     flush(pending)
                 pending = out
@@ -513,9 +595,62 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
                                                       leg["wer_fake"])) + "\n")
             generator.save_weights(os.path.join(generator_save_dir, str(epoch_idx + 1), 'cktp-' + str(epoch_idx + 1)))
             recognizer.save_weights(os.path.join(recognizer_save_dir, str(epoch_idx + 1), 'cktp-' + str(epoch_idx + 1)))
+            if avg is not None:
+                _save_averaged_generator(avg, os.path.join(checkpoint_prefix, 'generator_ema', str(epoch_idx + 1), 'cktp-' + str(epoch_idx + 1)),
+                                         ema_standing_batches, my_imgs, random_words, bucket_size, batch_size)
+                if fake_labels is not None:
+                    from .legibility import LEGIBILITY_HEADER, epoch_legibility
+                    with avg.applied():
+                        leg = epoch_legibility(generator, recognizer, image_batch, label_batch, style, fake_labels)
+                    leg_path = os.path.join(model_path, "legibility_ema.csv")
+                    new = not os.path.exists(leg_path)
+                    with open(leg_path, "a") as f:
+                        if new:
+                            f.write(LEGIBILITY_HEADER)
+                        f.write(",".join(str(v) for v in (epoch_idx + 1, leg["n"], leg["cer_real"], leg["wer_real"], leg["cer_fake"],
+                                                          leg["wer_fake"])) + "\n")
+            if samples_every > 0 and (epoch_idx + 1) % samples_every == 0:
+                _save_sample_sheet(generator, avg, my_imgs, seed_labels[1], os.path.join(gen_path, 'image_at_epoch_{:04d}.png'.format(epoch_idx + 1)))
             if state_path is not None:
                 save_training_state(state_path, generator, discriminator, recognizer, style_promoter, generator_optimizer,
-                                    discriminator_optimizer, recognizer_optimizer, stylepromoter_optimizer, epoch_idx, batch_per_epoch)
+                                    discriminator_optimizer, recognizer_optimizer, stylepromoter_optimizer, epoch_idx, batch_per_epoch,
+                                    averages=averages, streams=avg is not None)
+
+
+def _stack_images(imgs):
+    return torch.stack(list(imgs), 0) if torch.is_tensor(imgs[0]) else np.stack([np.asarray(m) for m in imgs], 0)
+
+
+def _save_averaged_generator(avg, prefix, standing_batches, my_imgs, random_words, bucket_size, batch_size):
+    """The per-epoch file of the averaged generator.  standing_batches > 0: its BatchNorm statistics are first re-estimated over
+    that many batches of `random.choices(my_imgs)` and fake words -- `random`'s state is put back, training draws what it would
+    have drawn anyway.  0: the file carries the live generator's statistics."""
+    from .averaging import standing_statistics
+    if standing_batches > 0:
+        host = random.getstate()
+        try:
+            batches = []
+            for _ in range(standing_batches):
+                style = _stack_images(random.choices(my_imgs, k=batch_size))
+                batches.append((style, draw_fake_labels(random_words, bucket_size, batch_size)[1]))
+        finally:
+            random.setstate(host)
+        with avg.applied():
+            standing_statistics(avg, batches)
+    avg.save_weights(prefix)
+
+
+def _save_sample_sheet(generator, avg, my_imgs, labels, path, cols=4, pad=2):
+    """image_at_epoch_NNNN.png: the words `labels` in the styles of the first len(labels) entries of `my_imgs`."""
+    import contextlib
+    from PIL import Image
+    from .averaging import sample_sheet
+    labels = np.asarray(labels, np.int32)
+    style = _stack_images([my_imgs[i % len(my_imgs)] for i in range(len(labels))])
+    with (avg.applied() if avg is not None else contextlib.nullcontext()):
+        sheet = sample_sheet(generator, style, labels, cols=cols, pad=pad)
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    Image.fromarray(sheet).save(path)                        # (2-D uint8: mode "L")
 
 
 # ------------------------------------------------------------------------------------------------

@@ -5,7 +5,8 @@ setup_optimizer :25-35, shared_specs (get_shared_specs) :38-40, io (setup_io) :4
 
 `--synthetic` swaps the IAM bucket folders (absent offline) for the synthetic generators of
 SURVEY section 8(d); everything downstream (factories, optimizers, train loop) is the same code.
-The dataset conversion (dinterface), PNG grids and GIF writer of the reference are out of scope."""
+`--ema-decay D` keeps an averaged generator (averaging.py), `--samples-every N` writes the reference's per-epoch picture
+image_at_epoch_NNNN.png.  The dataset conversion (dinterface) and GIF writer of the reference are out of scope."""
 from __future__ import annotations
 
 import argparse
@@ -78,7 +79,7 @@ def synthetic_dataset(batch_size, in_dim, bucket_size, n_classes, seed=0):
         yield images, labels
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gin", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "configs",
                                                   "scrabble_gan_mi355x.gin"))
@@ -94,7 +95,26 @@ def main(argv=None):
                     help="no float-atomic reduction splits in the conv kernels: bitwise reproducible runs, a few percent slower")
     ap.add_argument("--legibility-every", type=int, default=0,
                     help="after every Nth epoch append R's character / word error rates on real and generated words to <model_dir>/legibility.csv")
+    ap.add_argument("--ema-decay", type=float, default=0.0,
+                    help="> 0: keep an exponential moving average of the generator's weights (e.g. 0.9999) and write it per epoch to "
+                         "<checkpoints>/generator_ema/<e>/cktp-<e>; 0 (default): off")
+    ap.add_argument("--ema-start", type=int, default=0, help="the average is a plain copy of the weights for this many steps")
+    ap.add_argument("--ema-standing-batches", type=int, default=0,
+                    help="re-estimate the averaged generator's BatchNorm statistics over this many batches before it is saved / evaluated")
+    ap.add_argument("--samples-every", type=int, default=0,
+                    help="after every Nth epoch write <gen_imgs_dir>/image_at_epoch_NNNN.png (the averaged generator's when --ema-decay is on)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if not 0.0 <= args.ema_decay < 1.0:
+        ap.error("--ema-decay must be in [0, 1)")
+    if min(args.ema_start, args.ema_standing_batches, args.samples_every) < 0:
+        ap.error("--ema-start, --ema-standing-batches and --samples-every must be >= 0")
+    if args.ema_standing_batches and not args.ema_decay:
+        ap.error("--ema-standing-batches needs --ema-decay")
 
     # Data parallel (one process per GPU under torch.distributed.run): join the job BEFORE any GPU work, give every rank the
     # same host RNG streams (bucket choice, fake words, style images: every rank must see the same global batch and take its
@@ -138,7 +158,8 @@ def main(argv=None):
           epochs, m_path, latent_dim, gen_path, loss_fn, disc_iters, apply_gradient_balance, random_words, bucket_size, char_vec,
           max_batches_per_epoch=args.steps,
           state_path=os.path.join(ckpt_path, "state", "latest.safetensors") if args.resumable else None,
-          legibility_every=args.legibility_every)
+          legibility_every=args.legibility_every, ema_decay=args.ema_decay, ema_start=args.ema_start,
+          ema_standing_batches=args.ema_standing_batches, samples_every=args.samples_every)
 
 
 if __name__ == "__main__":

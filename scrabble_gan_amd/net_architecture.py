@@ -375,7 +375,9 @@ class GeneratorModel(_Model):
             return {k: self.store.p["NL_" + n + "." + k] for k in ("theta", "phi", "g", "o")}
         return nl if nl is not None else nn.nonlocal_weights(C, self.nl_gen, self.device)
 
-    def forward(self, style, y, nl_style=None, nl_up=None, training=True):
+    def forward(self, style, y, nl_style=None, nl_up=None, training=True, momentum=0.99):
+        """`momentum`: of the seven moving-statistics updates of a training-mode pass (0.99 = Keras' default, the train step's;
+        averaging.standing_statistics passes i / (i + 1) for a running mean over batches)."""
         S = self._pass_store()
         p = S.p
         style = _as_nhwc1(style, self.device)
@@ -386,7 +388,7 @@ class GeneratorModel(_Model):
         up_ctx = []
         for i, n in enumerate(self.up_names):
             if training:
-                net, c = nn.block_up_fwd(net, z, i + 1, S, n, i == len(self.up_names) - 1, self.reducer)
+                net, c = nn.block_up_fwd(net, z, i + 1, S, n, i == len(self.up_names) - 1, self.reducer, momentum=momentum)
             else:
                 net, c = _block_up_infer(net, z, i + 1, S, n, i == len(self.up_names) - 1), None
             nlc = None
@@ -395,7 +397,7 @@ class GeneratorModel(_Model):
             up_ctx.append((c, nlc))
         if training:
             yb, bctx = nn.bn_train_fwd(net, p["bn.gamma"], p["bn.beta"], False, True, self.reducer)   # :281-282
-            ops.bn_update_moving(p["bn.mm"], p["bn.mv"], bctx[2], bctx[3], bctx[5])
+            ops.bn_update_moving(p["bn.mm"], p["bn.mv"], bctx[2], bctx[3], bctx[5], momentum)
         else:
             yb, bctx = ops.bn_apply(net, p["bn.mm"], p["bn.mv"], p["bn.gamma"], p["bn.beta"], False, True), None
         img = ops.conv2d_fwd(yb, p["final.w"], p["final.b"], tanh_out=True)        # :283-289

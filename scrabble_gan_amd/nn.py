@@ -433,14 +433,15 @@ def block_up_specs(pre: str, cin: int, cout: int):
             (pre + ".cbn2.mm", (cout,), zeros, False), (pre + ".cbn2.mv", (cout,), ones, False)]
 
 
-def _cbn_fwd(x, z, zi: int, S: ParamStore, pre: str, reducer: Reducer, update_moving: bool):
-    """z [B,128]; this block's conditioning chunk is z[:, 32*zi : 32*zi+32] (net_architecture.py:260-262)."""
+def _cbn_fwd(x, z, zi: int, S: ParamStore, pre: str, reducer: Reducer, update_moving: bool, momentum: float = 0.99):
+    """z [B,128]; this block's conditioning chunk is z[:, 32*zi : 32*zi+32] (net_architecture.py:260-262).
+    `momentum`: of the moving-statistics update (Keras' 0.99; averaging.standing_statistics passes i / (i + 1))."""
     B, C = x.shape[0], x.shape[-1]
     gamma = ops.gemm(z, S.p[pre + ".gamma.w"], B, C, 32, 128, C, A_off=32 * zi)       # resnet_ops.py:18-21
     beta = ops.gemm(z, S.p[pre + ".beta.w"], B, C, 32, 128, C, A_off=32 * zi)         # :24-27
     y, ctx = bn_train_fwd(x, gamma, beta, True, True, reducer)
     if update_moving:
-        ops.bn_update_moving(S.p[pre + ".mm"], S.p[pre + ".mv"], ctx[2], ctx[3], ctx[5])
+        ops.bn_update_moving(S.p[pre + ".mm"], S.p[pre + ".mv"], ctx[2], ctx[3], ctx[5], momentum)
     return y, ctx
 
 
@@ -455,12 +456,12 @@ def _cbn_bwd(ctx, dy, z, dz, zi: int, S: ParamStore, pre: str, reducer: Reducer)
     return dx
 
 
-def block_up_fwd(x, z, zi: int, S: ParamStore, pre: str, is_last: bool, reducer: Reducer = LOCAL, update_moving=True):
+def block_up_fwd(x, z, zi: int, S: ParamStore, pre: str, is_last: bool, reducer: Reducer = LOCAL, update_moving=True, momentum: float = 0.99):
     p = S.p
     stride = (2, 1) if is_last else (2, 2)                                                    # :54
-    y1, c1 = _cbn_fwd(x, z, zi, S, pre + ".cbn1", reducer, update_moving)                     # :50-51
+    y1, c1 = _cbn_fwd(x, z, zi, S, pre + ".cbn1", reducer, update_moving, momentum)           # :50-51
     t = ops.conv2d_transpose_fwd(y1, p[pre + ".convT.w"], p[pre + ".convT.b"], stride=stride)   # :57-59
-    y2, c2 = _cbn_fwd(t, z, zi, S, pre + ".cbn2", reducer, update_moving)                     # :62-63
+    y2, c2 = _cbn_fwd(t, z, zi, S, pre + ".cbn2", reducer, update_moving, momentum)           # :62-63
     out = ops.conv2d_fwd(y2, p[pre + ".conv.w"], p[pre + ".conv.b"])                          # :65-66
     ops.conv2d_transpose_fwd(x, p[pre + ".short.w"], p[pre + ".short.b"], stride=stride, out=out, accum=True)   # :69-73
     return out, (x, c1, c2, stride)

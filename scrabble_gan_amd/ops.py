@@ -1602,6 +1602,43 @@ def rmsprop_update(p, g, ms, lr, rho=0.9, eps=1e-7):
     weights_changed()
 
 
+# ---------------------------------------------------------------- averaged generator (averaging.py)
+def ema_update(ema, p, one_minus_decay: float):
+    """ema += one_minus_decay * (p - ema) in place over two flat buffers.  `one_minus_decay` is 1 - decay as the caller computed
+    it in double; it is rounded to fp32 once, here.  0 leaves `ema` bitwise unchanged, 1 makes it bitwise `p`."""
+    _chk(ema, p)
+    if ema.numel() != p.numel():
+        raise ValueError("ema_update: %d vs %d elements" % (ema.numel(), p.numel()))
+    with _hbm("ema", ema, p, ema):
+        call("sg_ema_update", _p(ema), _p(p), ema.numel(), float(one_minus_decay), _stream())
+
+
+def swap_buffers(a, b):
+    """a <-> b in place (two flat buffers of one size).  Parameters rewritten through raw pointers: a caller that swaps a
+    model's weights calls weights_changed()."""
+    _chk(a, b)
+    if a.numel() != b.numel():
+        raise ValueError("swap_buffers: %d vs %d elements" % (a.numel(), b.numel()))
+    with _hbm("ema", a, b, a, b):
+        call("sg_swap_f32", _p(a), _p(b), a.numel(), _stream())
+
+
+def image_sheet_u8(imgs, cols: int, pad: int = 2, fill: int = 255):
+    """imgs [N,H,W,1] (or [N,H,W]) in [-1,1] -> uint8 [rows*(H+pad)-pad, cols*(W+pad)-pad] on the device: image i in cell
+    (i // cols, i % cols), pixel round(clip((x + 1) / 2, 0, 1) * 255), gutters and unused cells `fill`."""
+    _chk(imgs)
+    if imgs.dim() == 4 and imgs.shape[-1] == 1:
+        imgs = imgs.view(imgs.shape[:3])
+    if imgs.dim() != 3 or imgs.shape[0] < 1 or cols < 1 or pad < 0 or not 0 <= fill <= 255:
+        raise ValueError("image_sheet_u8: imgs %s, cols %r, pad %r, fill %r" % (tuple(imgs.shape), cols, pad, fill))
+    N, H, W = imgs.shape
+    rows = (N + cols - 1) // cols
+    sheet = torch.empty(rows * (H + pad) - pad, cols * (W + pad) - pad, device=imgs.device, dtype=torch.uint8)
+    with _hbm("elementwise", imgs, sheet):
+        call("sg_image_sheet_u8", _p(imgs), sheet.data_ptr(), N, H, W, int(cols), int(pad), int(fill), _stream())
+    return sheet
+
+
 def spectral_norm(w, u, power_iteration=1):
     _chk(w, u)
     N = w.shape[-1]
