@@ -1685,8 +1685,12 @@ def mul_mask(x, mask, rows_per_mask=1):
     """x [rows, cols] (any leading shape) times mask[rows / rows_per_mask, cols]."""
     _chk(x, mask)
     cols = x.shape[-1]
+    rows = x.numel() // cols
+    if rows_per_mask < 1 or rows % rows_per_mask or mask.numel() != (rows // rows_per_mask) * cols:      # (the kernel indexes the mask unchecked)
+        raise ValueError("mul_mask: x %s (%d rows) with rows_per_mask %r does not fit a mask of shape %s"
+                         % (tuple(x.shape), rows, rows_per_mask, tuple(mask.shape)))
     out = torch.empty_like(x)
-    call("sg_mul_mask", _p(x), _p(mask), _p(out), x.numel() // cols, cols, int(rows_per_mask), _stream())
+    call("sg_mul_mask", _p(x), _p(mask), _p(out), rows, cols, int(rows_per_mask), _stream())
     return out
 
 
