@@ -5,13 +5,16 @@
 // All kernels are HBM-bound sweeps over x[B, HW, C] with float4 channel vectors; the cross-row
 // reductions are wavefront/LDS trees inside a workgroup, then a tiny second stage in fp64 so that
 // E[x^2]-mean^2 keeps fp32-level accuracy (and so that data-parallel ranks can all-reduce the
-// fp64 sums between the two stages: SyncBN).
+// fp64 sums between the two stages: SyncBN).  The fp32 first stage sums x - x0 and (x - x0)^2 with
+// x0 = the block's first row, and the second stage puts the shift back in fp64: the fp32 rounding
+// is relative to the spread of the block, not to mean^2, and one row (or a constant channel)
+// gives var = 0 exactly.
 #include "sg_common.h"
 
 #define F4(p) (*reinterpret_cast<float4*>(p))
 #define CF4(p) (*reinterpret_cast<const float4*>(p))
 
-// stage 1: partial[blk][0][c] = sum x, partial[blk][1][c] = sum x^2 over the block's rows
+// stage 1: partial[blk][0][c] = sum (x - x0), partial[blk][1][c] = sum (x - x0)^2 over the block's rows, x0 = its first row
 __global__ __launch_bounds__(256) void k_bn_stats_partial(const float* x, float* partial, long M, int C, int rows_per_block) {
   __shared__ float4 r1[256], r2[256];
   const int cqn = C >> 2;
@@ -20,10 +23,12 @@ __global__ __launch_bounds__(256) void k_bn_stats_partial(const float* x, float*
   while (lanes * 2 * cqn <= 256) lanes *= 2;
   const long m0 = (long)blockIdx.x * rows_per_block, m1 = min(M, m0 + rows_per_block);
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s;
+  const float4 x0 = rl < lanes ? CF4(x + m0 * C + 4 * cq) : s;      // (m0 < M: the grid is cdiv(M, rows_per_block))
   for (long m = m0 + rl; m < m1 && rl < lanes; m += lanes) {
     const float4 v = CF4(x + m * C + 4 * cq);
-    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    q.x += v.x * v.x; q.y += v.y * v.y; q.z += v.z * v.z; q.w += v.w * v.w;
+    const float4 d = make_float4(v.x - x0.x, v.y - x0.y, v.z - x0.z, v.w - x0.w);
+    s.x += d.x; s.y += d.y; s.z += d.z; s.w += d.w;
+    q.x += d.x * d.x; q.y += d.y * d.y; q.z += d.z * d.z; q.w += d.w * d.w;
   }
   r1[threadIdx.x] = s; r2[threadIdx.x] = q;
   __syncthreads();
@@ -42,15 +47,24 @@ __global__ __launch_bounds__(256) void k_bn_stats_partial(const float* x, float*
   }
 }
 
-// stage 2: sums[0][c], sums[1][c] (fp64) = sum over blocks.  16 columns x 16 block-lanes per workgroup: each thread
-// adds every 16th partial (independent loads, short chain), then an LDS tree over the lanes in fp64.
-__global__ __launch_bounds__(256) void k_bn_stats_combine(const float* partial, double* sums, int nblk, int C) {
+// stage 2: sums[0][c] = sum x, sums[1][c] = sum x^2 (fp64) over blocks, the shift of each block put back in fp64:
+// sum x = s + n x0, sum x^2 = q + 2 x0 s + n x0^2 (n rows in the block).  16 columns x 16 block-lanes per workgroup: each
+// thread adds every 16th partial (independent loads, short chain), then an LDS tree over the lanes in fp64.
+__global__ __launch_bounds__(256) void k_bn_stats_combine(const float* partial, const float* x, double* sums, int nblk, int C, long M,
+                                                          int rows_per_block) {
   __shared__ double red[256];
   const int cl = threadIdx.x & 15, bl = threadIdx.x >> 4;
   const int c = blockIdx.x * 16 + cl;
   double s = 0.0;
-  if (c < 2 * C)
-    for (int b = bl; b < nblk; b += 16) s += (double)partial[(size_t)b * 2 * C + c];
+  if (c < 2 * C) {
+    const int ch = c < C ? c : c - C;
+    for (int b = bl; b < nblk; b += 16) {
+      const long m0 = (long)b * rows_per_block;
+      const double nb = (double)(min(M, m0 + rows_per_block) - m0);
+      const double x0 = (double)x[m0 * C + ch], sb = (double)partial[(size_t)b * 2 * C + ch];
+      s += c < C ? sb + nb * x0 : (double)partial[(size_t)b * 2 * C + c] + 2.0 * x0 * sb + nb * x0 * x0;
+    }
+  }
   red[threadIdx.x] = s;
   __syncthreads();
   for (int st = 8; st > 0; st >>= 1) {
@@ -211,10 +225,10 @@ extern "C" long sg_bn_stats_workspace_floats(long M, int C) { return (long)sg_cd
 
 // sums (fp64, [2*C]) = per-channel sum and sum of squares over the M rows of x
 extern "C" int sg_bn_stats_sums(const float* x, long M, int C, float* workspace, double* sums, void* stream) {
-  if (!x || !workspace || !sums || !chan_ok(C)) return SG_ERR_ARG;
+  if (!x || !workspace || !sums || !chan_ok(C) || M < 1) return SG_ERR_ARG;
   const int rpb = bn_stats_rpb(M), nblk = sg_cdiv(M, rpb);
   SG_KERNEL(k_bn_stats_partial, dim3(nblk), dim3(256), 0, (hipStream_t)stream, x, workspace, M, C, rpb);
-  SG_KERNEL(k_bn_stats_combine, dim3(sg_cdiv(2 * C, 16)), dim3(256), 0, (hipStream_t)stream, workspace, sums, nblk, C);
+  SG_KERNEL(k_bn_stats_combine, dim3(sg_cdiv(2 * C, 16)), dim3(256), 0, (hipStream_t)stream, workspace, x, sums, nblk, C, M, rpb);
   return sg_launch_status();
 }
 
