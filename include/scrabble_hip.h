@@ -375,6 +375,21 @@ int sg_ema_update(float* ema, const float* p, long n, float one_minus_decay, voi
 int sg_swap_f32(float* a, float* b, long n, void* stream);
 int sg_image_sheet_u8(const float* imgs, unsigned char* sheet, int N, int H, int W, int cols, int pad, int fill, void* stream);
 
+/* ---- differentiable augmentation of the discriminator's inputs (scrabble_gan_amd/augment.py; csrc/augment.hip; not in the
+ * reference: DiffAugment, Zhao et al. 2020).  x, y, dy, dx [B,H,W,C] fp32; params [B,12] fp32, one row per sample:
+ *   c beta | a00 a01 a02 a10 a11 a12 | x0 y0 x1 y1        (identity: 1 0 | 1 0 0 0 1 0 | 0 0 0 0)
+ * sg_augment_fwd: mean_out[b] = mu_b = mean of x_b (fp64 accumulation); t(v) = c v + (1 - c) mu_b + beta;
+ *   y[b,i,j,:] = pad inside the half-open cutout rectangle [x0,x1) x [y0,y1) (integer-valued; empty when x1 <= x0 or y1 <= y0),
+ *   elsewhere the bilinear combination of the four taps around sx = a00 j + a01 i + a02, sy = a10 j + a11 i + a12 (pixel
+ *   units): a tap inside the image gives w t(x[tap]), a tap outside w pad, a tap of weight exactly 0 is not read.
+ * sg_augment_bwd: dx (overwritten) = the exact adjoint: c w dy routed to the inside taps of the non-cut pixels, plus
+ *   (1 - c) / (H W C) * (sum of w dy over them) on every element of the sample.  A gather with one adder per address: bitwise
+ *   reproducible.  Its search window holds for rows within the limits of augment.DiffAugment.check (a10 == 0, 0.9 <= a00,
+ *   a11 <= 1.1, |a01| <= 0.3, |a02|, |a12| <= 65536).
+ * Output and input are distinct buffers.  SG_ERR_ARG: a null pointer, x == y, B / H / W / C < 1, H W C > 2^31 - 1. */
+int sg_augment_fwd(const float* x, const float* params, float* y, float* mean_out, int B, int H, int W, int C, float pad, void* stream);
+int sg_augment_bwd(const float* dy, const float* params, float* dx, int B, int H, int W, int C, void* stream);
+
 /* ---- collective of the data-parallel step (the reference has none: BASELINE.json north_star) ----------
  * SUM all-reduce, in place, of `n` elements of a flat device buffer over RCCL on `stream`; gradients are sums over the
  * batch (reference data_utils.py:450,454,458,467 differentiate [B,1] targets), so ranks ADD.  comm = the ncclComm_t made by

@@ -108,7 +108,7 @@ DEBUG_KEEP = None      # tests set a dict here to receive the generator's saved 
 def train_step(epoch_idx, batch_idx, batch_per_epoch, images, labels, discriminator, recognizer, style_promoter, composite_gan,
                generator_optimizer, discriminator_optimizer, recognizer_optimizer, stylepromoter_optimizer, my_imgs,
                batch_size, latent_dim, loss_fn, disc_iters, apply_gradient_balance, random_words, bucket_size, gen_path,
-               fake_labels=None, nl=None, verbose=True, sync=True, fuse_passes=True, share_backward=True):
+               fake_labels=None, nl=None, verbose=True, sync=True, fuse_passes=True, share_backward=True, augment=None):
     """One optimisation step (data_utils.py:358-473).
 
     Extra keyword arguments (not in the reference): `fake_labels` overrides the host draw of :386-387
@@ -118,6 +118,9 @@ def train_step(epoch_idx, batch_idx, batch_per_epoch, images, labels, discrimina
     StepScalars sequence that waits for its device-to-host copy on first access; `fuse_passes=False`
     keeps every reference call a separate pass even when the input widths match; `share_backward=False` runs the
     weight-gradient and image-gradient sweeps through D(x_f) / S(x_f) separately, as the reference's tapes do.
+    `augment` (an augment.DiffAugment, or a (params_fake, params_real[, pad]) tuple of device tables for this rank's samples):
+    D sees ops.augment(x_f) and ops.augment(images) and the image gradient of D's sweep goes back through ops.augment_bwd; S and
+    R see the images as they are.  None (default): nothing is drawn or launched that was not before.
     """
     G = composite_gan.generator
     D, R, S = discriminator, recognizer, style_promoter
@@ -140,6 +143,7 @@ def train_step(epoch_idx, batch_idx, batch_per_epoch, images, labels, discrimina
     if isinstance(my_imgs, (list, tuple)):
         my_imgs = np.stack([np.asarray(m) for m in my_imgs], axis=0) if not torch.is_tensor(my_imgs[0]) else torch.stack(list(my_imgs), 0)
     style = _as_nhwc1(my_imgs, dev)
+    n_global = images.shape[0]
     if red.world_size > 1 and getattr(red, "shard_inputs", True):       # data parallel: this rank's slice of every per-step tensor
         images, labels_t, fake_t, style = (red.shard(t) for t in (images, labels_t, fake_t, style))
     L_r, L_f = labels_t.shape[1], fake_t.shape[1]
@@ -170,6 +174,12 @@ def train_step(epoch_idx, batch_idx, batch_per_epoch, images, labels, discrimina
     if DEBUG_KEEP is not None:
         DEBUG_KEEP["ctx_g"] = ctx_g                                 # (tests: the ReLU decisions the forward pass took)
     B = x_f.shape[0]
+    x_fd, images_d, aug_ctx = x_f, images, None                     # what D sees
+    if augment is not None:
+        from .augment import step_tables
+        aug_pf, aug_pr, aug_pad = step_tables(augment, n_global, x_f.shape[1:3], images.shape[1:3], dev, red)
+        x_fd, aug_ctx = ops.augment(x_f, aug_pf, aug_pad)
+        images_d, _ = ops.augment(images, aug_pr, aug_pad)
     il_f, il_r = ctc_input_length(L_f), ctc_input_length(L_r)
     plain = all(getattr(m, "supports_fused_passes", True) for m in (D, S))     # (make_my_discriminator: separate passes and sweeps)
     fuse = fuse_passes and plain and x_f.shape == images.shape
@@ -182,7 +192,7 @@ def train_step(epoch_idx, batch_idx, batch_per_epoch, images, labels, discrimina
             nls = [nl.get("S.fake"), nl.get("S.style"), nl.get("S.real")]
             with ops.net_stream(x_f, style, images, *[t for d in nls if d is not None for t in d.values()]) as ns_f:
                 (s_f, s_my, s_r), ctx_S, _ = S.forward_multi([x_f, style, images], nls)
-        (d_f, d_r), ctx_D, _ = D.forward_multi([x_f, images], [nl.get("D.fake"), nl.get("D.real")])
+        (d_f, d_r), ctx_D, _ = D.forward_multi([x_fd, images_d], [nl.get("D.fake"), nl.get("D.real")])
         if use_ns:
             pass
         elif fuse_style:
@@ -197,10 +207,10 @@ def train_step(epoch_idx, batch_idx, batch_per_epoch, images, labels, discrimina
             r_f, ctx_rf = R.forward(x_f, fake_t, il_f, L_f, training=True)
             r_r, ctx_rr = R.forward(images, labels_t, il_r, L_r, training=True)
     else:
-        d_f, ctx_df = D.forward(x_f, nl.get("D.fake"))
+        d_f, ctx_df = D.forward(x_fd, nl.get("D.fake"))
         s_f, ctx_sf = S.forward(x_f, nl.get("S.fake"))
         r_f, ctx_rf = R.forward(x_f, fake_t, il_f, L_f, training=True)
-        d_r, ctx_dr = D.forward(images, nl.get("D.real"))
+        d_r, ctx_dr = D.forward(images_d, nl.get("D.real"))
         s_my, ctx_smy = S.forward(style, nl.get("S.style"))
         s_r, ctx_sr = S.forward(images, nl.get("S.real"))
         r_r, ctx_rr = R.forward(images, labels_t, il_r, L_r, training=True)
@@ -296,6 +306,8 @@ def train_step(epoch_idx, batch_idx, batch_per_epoch, images, labels, discrimina
             dx_d = D.backward(D.slice_ctx(ctx_D, 0, B) if fuse else ctx_df, gG_d, want_dx=True, want_dw=False)
         if dx_s is None:
             dx_s = S.backward(S.slice_ctx(ctx_S, 0, B) if fuse else ctx_sf, gG_s, want_dx=True, want_dw=False)
+        if aug_ctx is not None:
+            dx_d = ops.augment_bwd(dx_d, aug_ctx)                   # D saw augment(x_f): its image gradient goes back through the adjoint
         dx = ops.add(dx_d, dx_s, out=dx_d)
         ctx_rf_ = R.slice_ctx(ctx_R, 0, B) if (fuse and fuse_r) else ctx_rf
         ops.add(dx, R.backward(ctx_rf_, gG_r, want_dx=True, want_dw=False), out=dx)
@@ -422,11 +434,12 @@ def _restore_streams(st, models) -> bool:
 
 
 def save_training_state(path, generator, discriminator, recognizer, style_promoter, generator_optimizer, discriminator_optimizer,
-                        recognizer_optimizer, stylepromoter_optimizer, epoch_idx=0, batch_idx=0, averages=None, streams=False):
+                        recognizer_optimizer, stylepromoter_optimizer, epoch_idx=0, batch_idx=0, averages=None, streams=False, augment=None):
     """`averages` (optional): {"G": averaging.WeightAverage} -- its buffer, update counter and standing statistics are stored under
     `G.ema/...`.  `streams=True` also stores the random streams of the run (`rng/...`: `random`, numpy, the models' generators): an
     average is a function of the whole trajectory, so a resumed run continues it exactly only if it draws what the uninterrupted run
-    would have drawn.  Without either the file has the keys it always had."""
+    would have drawn; with `augment` (an augment.DiffAugment) the sampler's stream goes with them as `rng/augment`.  Without either
+    the file has the keys it always had."""
     from safetensors.torch import save_file
     out = {"position": torch.tensor([int(epoch_idx), int(batch_idx)], dtype=torch.int64)}
     for tag, m, opt in (("G", generator, generator_optimizer), ("D", discriminator, discriminator_optimizer),
@@ -440,6 +453,8 @@ def save_training_state(path, generator, discriminator, recognizer, style_promot
             out["%s.ema/%s" % (tag, k)] = v.contiguous()
     if streams:
         out.update(_stream_states((("G", generator), ("D", discriminator), ("R", recognizer), ("S", style_promoter))))
+        if augment is not None:
+            out["rng/augment"] = torch.tensor(augment.state_words(), dtype=torch.int64)
     d = os.path.dirname(path)
     if d:
         os.makedirs(d, exist_ok=True)
@@ -448,10 +463,10 @@ def save_training_state(path, generator, discriminator, recognizer, style_promot
 
 
 def load_training_state(path, generator, discriminator, recognizer, style_promoter, generator_optimizer, discriminator_optimizer,
-                        recognizer_optimizer, stylepromoter_optimizer, averages=None, streams=False):
+                        recognizer_optimizer, stylepromoter_optimizer, averages=None, streams=False, augment=None):
     """Restores what save_training_state wrote; -> (epoch_idx, batch_idx) of the save.  `averages` = {"G": WeightAverage}: restored from
     the `G.ema/...` tensors; with a state written without them the average restarts as a copy of the loaded weights.
-    `streams=True` puts the saved random streams (`rng/...`) back when the file has them."""
+    `streams=True` puts the saved random streams (`rng/...`) back when the file has them, `rng/augment` into `augment`."""
     from safetensors.torch import load_file
     st = load_file(path)
     for tag, m, opt in (("G", generator, generator_optimizer), ("D", discriminator, discriminator_optimizer),
@@ -468,6 +483,8 @@ def load_training_state(path, generator, discriminator, recognizer, style_promot
             avg.flat.copy_(avg.model.store.flat)
     if streams:                                           # (a state written without them: the streams stay where they are)
         _restore_streams(st, (("G", generator), ("D", discriminator), ("R", recognizer), ("S", style_promoter)))
+        if augment is not None and "rng/augment" in st:
+            augment.set_state_words(st["rng/augment"].tolist())
     ops.weights_changed()
     pos = st["position"].tolist()
     return int(pos[0]), int(pos[1])
@@ -481,7 +498,7 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
           generator_optimizer, discriminator_optimizer, recognizer_optimizer, stylepromoter_optimizer, my_imgs,
           seed_labels, buffer_size, batch_size, epochs, model_path, latent_dim, gen_path, loss_fn, disc_iters,
           apply_gradient_balance, random_words, bucket_size, char_vector, max_batches_per_epoch=None, state_path=None,
-          ema_decay=0.0, ema_start=0, ema_standing_batches=0, samples_every=0, legibility_every=0):
+          ema_decay=0.0, ema_start=0, ema_standing_batches=0, samples_every=0, augment="", augment_p=1.0, legibility_every=0):
     """Epoch/batch loop, 16-column ';' summaries and per-epoch G/R weight saves (data_utils.py:198-352).
     The summary rows carry the ';' the reference drops between g_loss_std and s_loss (Appendix C-10).
     `state_path` (not in the reference): full training state written there after every epoch and, when the file exists
@@ -500,8 +517,12 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
     skips the batches of the finished epochs, so it continues the average exactly.
     `samples_every` = N > 0: after every Nth epoch <gen_path>/image_at_epoch_NNNN.png (the reference's per-epoch picture,
     data_utils.py:493-519) shows the words `seed_labels[1]` in the styles of the first len(words) entries of `my_imgs`, rendered by the
-    averaged generator when there is one, else by G.  With all four at their defaults nothing is launched, drawn or written that
-    was not before."""
+    averaged generator when there is one, else by G.
+    `augment` (not in the reference): a comma-separated policy of augment.FAMILIES, e.g. "color,translation,cutout", or a ready
+    augment.DiffAugment -- D then sees only augmented images, real and generated, each family applied with probability `augment_p`
+    (train_step's `augment`).  The sampler has its own random stream; the full state (`state_path`) then carries the run's random
+    streams and the sampler's (`rng/augment`), and a resumed run skips the batches of the finished epochs, as with an average.
+    With all of these at their defaults nothing is launched, drawn or written that was not before."""
     generator_save_dir = os.path.join(checkpoint_prefix, 'generator/')
     recognizer_save_dir = os.path.join(checkpoint_prefix, 'recognizer/')
     # data parallel: every rank runs the loop (same seeded host streams -> same batches, each rank takes its slice inside
@@ -525,8 +546,13 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
         from .averaging import WeightAverage
         avg = WeightAverage(generator, decay=ema_decay, start_step=ema_start)
     averages = {"G": avg} if avg is not None else None
+    aug = None
+    if augment:
+        from .augment import DiffAugment
+        aug = augment if isinstance(augment, DiffAugment) else DiffAugment(augment, p=augment_p)
+    exact = avg is not None or aug is not None               # the state carries the random streams and a resumed run replays the dataset
     if state_path is not None and os.path.exists(state_path):
-        if avg is not None:
+        if exact:
             # the dataset's position is not part of the state: the batches of the finished epochs are drawn and dropped (before the
             # saved streams are put back), so the resumed run sees what the uninterrupted one would
             from safetensors import safe_open
@@ -536,7 +562,7 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
                 next(dataset)
         saved_epoch, _ = load_training_state(state_path, generator, discriminator, recognizer, style_promoter, generator_optimizer,
                                              discriminator_optimizer, recognizer_optimizer, stylepromoter_optimizer,
-                                             averages=averages, streams=avg is not None)
+                                             averages=averages, streams=exact, augment=aug)
         first_epoch = saved_epoch + 1
         print('resumed from %s: continuing with epoch %d' % (state_path, first_epoch + 1))
     mode = "a" if first_epoch > 0 else "w"                   # a resumed run appends to the summaries of the first one
@@ -568,7 +594,7 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
                                  style_promoter, composite_gan, generator_optimizer, discriminator_optimizer,
                                  recognizer_optimizer, stylepromoter_optimizer, my_img_batch, batch_size, latent_dim, loss_fn,
                                  disc_iters, apply_gradient_balance, random_words, bucket_size, gen_path, sync="lazy",
-                                 fake_labels=fake_labels)
+                                 fake_labels=fake_labels, augment=aug)
                 if avg is not None:
                     avg.update()                             # outside the step (and outside a captured one): one sweep over G's buffer
                 if pending is not None:
@@ -614,7 +640,7 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
             if state_path is not None:
                 save_training_state(state_path, generator, discriminator, recognizer, style_promoter, generator_optimizer,
                                     discriminator_optimizer, recognizer_optimizer, stylepromoter_optimizer, epoch_idx, batch_per_epoch,
-                                    averages=averages, streams=avg is not None)
+                                    averages=averages, streams=exact, augment=aug)
 
 
 def _stack_images(imgs):

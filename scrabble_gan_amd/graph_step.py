@@ -5,7 +5,8 @@ GPU time of the bf16 / fp8 steps at the 8-way shard batch (34 / 50 ms).  With fi
 the same every step, so it is captured ONCE (torch.cuda.CUDAGraph on ROCm = hipGraph; fresh capture in this process, nothing is
 re-executed) and each further step is one hipGraphLaunch.  What changes from step to step lives in device memory the graph
 reads: the input batch, the freshly drawn NonLocalBlock kernels (host QR per call, uploaded before the replay)
-and Adam's bias-corrected step size (sg_adam_update_dlr).  Single process, Adam optimizers, fixed word lengths; the data-parallel
+and Adam's bias-corrected step size (sg_adam_update_dlr) and, with `augment=`, the step's augmentation rows (augment.py: drawn on the
+host, uploaded into a static [2B,12] table before the replay).  Single process, Adam optimizers, fixed word lengths; the data-parallel
 exchange is not captured (world size 1)."""
 from __future__ import annotations
 
@@ -19,12 +20,13 @@ NL_NAMES = ("G.style", "G.up", "D.fake", "S.fake", "D.real", "S.style", "S.real"
 
 class GraphedStep:
     def __init__(self, discriminator, recognizer, style_promoter, composite_gan, optimizers, batch_size, loss_fn, apply_gradient_balance,
-                 warmup: int = 2):
+                 warmup: int = 2, augment=None):
         self.D, self.R, self.S, self.gan = discriminator, recognizer, style_promoter, composite_gan
         self.G = composite_gan.generator
         self.opts = list(optimizers)               # (generator, discriminator, recognizer, style promoter) as train_step takes them
         self.B, self.loss_fn, self.balance, self.warmup = batch_size, loss_fn, int(apply_gradient_balance), warmup
         self.graph = None
+        self.augment = augment                     # augment.DiffAugment or None
         if self.G.reducer.world_size != 1:
             raise ValueError("GraphedStep captures single-process steps only")
         if self.G.nl_mode != "reference":
@@ -63,6 +65,13 @@ class GraphedStep:
             self._lr_pinned[i] = o._lr_t()
             o.iterations -= 1                      # (apply_flat advances the counter itself in eager steps; replay() does it below)
         self._lr_dev.copy_(self._lr_pinned, non_blocking=True)
+        if self.augment is not None:               # fake rows, then real rows: train_step's own draw order
+            images, _labels, _my, fake_labels = self.inputs
+            H = images.shape[1]
+            pf, pr = self.augment.sample_pair(self.B, (H, H // 2 * fake_labels.shape[1]), tuple(images.shape[1:3]))
+            self._aug_pinned[:self.B].copy_(torch.from_numpy(pf))
+            self._aug_pinned[self.B:].copy_(torch.from_numpy(pr))
+            self._aug_dev.copy_(self._aug_pinned, non_blocking=True)
         self._copied = torch.cuda.Event()
         self._copied.record(torch.cuda.current_stream())
 
@@ -77,6 +86,9 @@ class GraphedStep:
         self._nl_dev = torch.empty(n, device=dev)
         self._lr_pinned = torch.empty(4, dtype=torch.float32, pin_memory=True)
         self._lr_dev = torch.empty(4, device=dev)
+        if self.augment is not None:
+            self._aug_pinned = torch.empty(2 * self.B, 12, dtype=torch.float32, pin_memory=True)
+            self._aug_dev = torch.empty(2 * self.B, 12, device=dev)
         self.nl, off = {}, 0
         for name, (C, _gen) in zip(NL_NAMES, self._nl_requests()):
             d = {}
@@ -108,8 +120,10 @@ class GraphedStep:
     def _run(self):
         images, labels, my_imgs, fake_labels = self.inputs
         o = self.opts
+        aug = None if self.augment is None else (self._aug_dev[:self.B], self._aug_dev[self.B:], self.augment.pad)
         return DU.train_step(0, 0, 1, images, labels, self.D, self.R, self.S, self.gan, o[0], o[1], o[2], o[3], my_imgs, self.B, 128,
-                             self.loss_fn, 1, self.balance, None, 10, "", fake_labels=fake_labels, nl=self.nl, verbose=False, sync=False)
+                             self.loss_fn, 1, self.balance, None, 10, "", fake_labels=fake_labels, nl=self.nl, verbose=False, sync=False,
+                             augment=aug)
 
     def step(self):
         """One optimisation step = upload of the step's host-drawn state + one graph launch.  -> StepScalars (lazy read-back)."""

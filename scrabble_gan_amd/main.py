@@ -6,7 +6,7 @@ setup_optimizer :25-35, shared_specs (get_shared_specs) :38-40, io (setup_io) :4
 `--synthetic` swaps the IAM bucket folders (absent offline) for the synthetic generators of
 SURVEY section 8(d); everything downstream (factories, optimizers, train loop) is the same code.
 `--ema-decay D` keeps an averaged generator (averaging.py), `--samples-every N` writes the reference's per-epoch picture
-image_at_epoch_NNNN.png.  The dataset conversion (dinterface) and GIF writer of the reference are out of scope."""
+image_at_epoch_NNNN.png, `--augment color,translation,cutout` shows D augmented images only (augment.py).  The dataset conversion (dinterface) and GIF writer of the reference are out of scope."""
 from __future__ import annotations
 
 import argparse
@@ -103,6 +103,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="re-estimate the averaged generator's BatchNorm statistics over this many batches before it is saved / evaluated")
     ap.add_argument("--samples-every", type=int, default=0,
                     help="after every Nth epoch write <gen_imgs_dir>/image_at_epoch_NNNN.png (the averaged generator's when --ema-decay is on)")
+    ap.add_argument("--augment", default="",
+                    help="differentiable augmentation of everything D sees, e.g. color,translation,cutout (families: color, translation, "
+                         "cutout, affine); empty (default): off")
+    ap.add_argument("--augment-p", type=float, default=1.0, help="probability with which each --augment family is applied to a sample")
     return ap
 
 
@@ -115,6 +119,13 @@ def main(argv=None):
         ap.error("--ema-start, --ema-standing-batches and --samples-every must be >= 0")
     if args.ema_standing_batches and not args.ema_decay:
         ap.error("--ema-standing-batches needs --ema-decay")
+    augment = ""
+    if args.augment:
+        from .augment import DiffAugment
+        try:
+            augment = DiffAugment(args.augment, p=args.augment_p, seed=args.seed)      # (every rank: the same seed, the same rows)
+        except ValueError as e:
+            ap.error(str(e))
 
     # Data parallel (one process per GPU under torch.distributed.run): join the job BEFORE any GPU work, give every rank the
     # same host RNG streams (bucket choice, fake words, style images: every rank must see the same global batch and take its
@@ -159,7 +170,7 @@ def main(argv=None):
           max_batches_per_epoch=args.steps,
           state_path=os.path.join(ckpt_path, "state", "latest.safetensors") if args.resumable else None,
           legibility_every=args.legibility_every, ema_decay=args.ema_decay, ema_start=args.ema_start,
-          ema_standing_batches=args.ema_standing_batches, samples_every=args.samples_every)
+          ema_standing_batches=args.ema_standing_batches, samples_every=args.samples_every, augment=augment)
 
 
 if __name__ == "__main__":

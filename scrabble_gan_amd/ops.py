@@ -1639,6 +1639,42 @@ def image_sheet_u8(imgs, cols: int, pad: int = 2, fill: int = 255):
     return sheet
 
 
+# ---------------------------------------------------------------- differentiable augmentation (augment.py)
+def _chk_augment(name: str, x, params):
+    _chk(x, params)
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError("%s: expected a non-empty [B,H,W,C] tensor, got %s" % (name, tuple(x.shape)))
+    if tuple(params.shape) != (x.shape[0], 12):
+        raise ValueError("%s: params must be [%d,12] (one row per sample), got %s" % (name, x.shape[0], tuple(params.shape)))
+
+
+def augment(x, params, pad: float = 0.0):
+    """y = the augmented batch of x [B,H,W,C] under the rows of params [B,12] (augment.py; include/scrabble_hip.h), and the context
+    augment_bwd needs.  y is a plain fp32 tensor without a bf16 / fp8 operand copy, like a batch of real images."""
+    _chk_augment("augment", x, params)
+    B, H, W, C = x.shape
+    y = torch.empty_like(x)
+    mean = torch.empty(B, device=x.device, dtype=torch.float32)
+    _touch(y)
+    with _hbm("elementwise", x, y):
+        call("sg_augment_fwd", _p(x), _p(params), _p(y), _p(mean), B, H, W, C, float(pad), _stream())
+    return y, (params, tuple(x.shape), mean)
+
+
+def augment_bwd(dy, ctx):
+    """dx = the adjoint of augment applied to dy (the gradient w.r.t. augment's input); bitwise reproducible."""
+    params, shape, _mean = ctx
+    _chk_augment("augment_bwd", dy, params)
+    if tuple(dy.shape) != shape:
+        raise ValueError("augment_bwd: dy %s, the forward pass saw %s" % (tuple(dy.shape), shape))
+    B, H, W, C = shape
+    dx = torch.empty_like(dy)
+    _touch(dx)
+    with _hbm("elementwise", dy, dx):
+        call("sg_augment_bwd", _p(dy), _p(params), _p(dx), B, H, W, C, _stream())
+    return dx
+
+
 def spectral_norm(w, u, power_iteration=1):
     _chk(w, u)
     N = w.shape[-1]
