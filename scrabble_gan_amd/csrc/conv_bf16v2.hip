@@ -182,13 +182,15 @@ __global__ __launch_bounds__((NWO ? NWO : (BMT == 256 ? 8 : 4)) * 64, 2) void sg
   const int HW = p.Hg * p.Wg;
   const int n_tiles = p.N / BN;
   int wg, split, nsplit;
-  if ((int)blockIdx.x < p.full_tiles) {
-    wg = sg2_xcd_remap(blockIdx.x, p.full_tiles);
+  int bid = (int)blockIdx.x;
+  if constexpr (ES == 4 && BMT == 128) bid += p.block0;      // (the tail launch behind sg_wino_persist_kernel starts at the first tail tile)
+  if (bid < p.full_tiles) {
+    wg = sg2_xcd_remap(bid, p.full_tiles);
     split = 0;
     nsplit = 1;
   } else {
     const int tail_tiles = p.n_tiles_total - p.full_tiles;
-    const int u = sg2_xcd_remap(blockIdx.x - p.full_tiles, tail_tiles * p.tail_split);
+    const int u = sg2_xcd_remap(bid - p.full_tiles, tail_tiles * p.tail_split);
     nsplit = p.tail_split;
     split = u / tail_tiles;
     wg = p.full_tiles + (u - split * tail_tiles);
@@ -691,6 +693,215 @@ __global__ __launch_bounds__((NWO ? NWO : (BMT == 256 ? 8 : 4)) * 64, 2) void sg
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// Persistent form of the grouped fp32 products (the Winograd-domain launches of conv_winograd.hip: 128 x 128 tiles, one tap, identity
+// output layout, no bias / mask / accumulate, every row live).  A workgroup of the one-tile kernel above issues stage 0, waits a full
+// memory round trip, passes a barrier, issues stage 1 and only then starts its matrix loop; with 16 k-tiles per tile at K = 512 that
+// prologue and the workgroup turn-over are a sizeable part of the tile.  Here min(full tiles, 2 x CUs) workgroups walk the tiles
+// vb = blockIdx.x, + gridDim.x, ... (through the same XCD remap, so the workgroups of an XCD stay on neighbouring tiles of one frequency
+// plane), and the k-tile stream does not stop at a tile boundary:
+//   * the load cursor runs over (tile, k-tile) pairs; a tile's last-but-one k-tile issues k-tile 0 of the NEXT tile into stage 0 (in the
+//     shadow of its last MFMA step, like any other k-tile), the next tile's operand bases are two 64-bit scalars computed once per tile;
+//   * the last k-tile issues nothing: behind its barrier stage 1 is free, and the epilogue stages the accumulators through the
+//     stage-1 regions (A stage 1 | B stage 1 = 32 KB: 32-row passes for four waves, 16-row passes for eight) while stage 0 already
+//     holds the next tile's first k-tile -- 64 KB per workgroup as before, two workgroups per CU;
+//   * the stores are issued and NOT waited for: one barrier (LDS only), k-tile 1 of the next tile goes into stage 1, the accumulators
+//     are re-zeroed and the loop continues; the first vmcnt(0) comes seven MFMA steps later.
+// The k-loop is the macro of the one-tile kernel, branch-free, phantom k-tile included (odd K / 32): per tile the same MFMAs in the
+// same order on the same operands -- results are bit-identical to the one-tile kernel's.
+template <int NW>
+__global__ __launch_bounds__(NW * 64, 2) void sg_wino_persist_kernel(const SgIgemm2Args p) {
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
+  typedef unsigned long long u64;
+  constexpr int BM = 128, BN = 128, BK = 32;
+  constexpr int ATILE = BM * 128, BTILE = BN * 128;
+  constexpr int WN = BN / 64, WM = NW / WN;
+  constexpr int TM = BM / WM / 32, TN = 2;
+  constexpr int NQ = BM / (8 * NW);                     // DMA instructions per thread and operand
+  constexpr int RP = 128 / NW;                          // rows of an epilogue pass (per wave: RP x 64 floats = 32 KB / NW of staging)
+  static_assert(NW == 4 || NW == 8, "four or eight waves");
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave / WN, wn = wave % WN;
+  const int n_tiles = p.N / BN;
+  const int KT = p.Ca / BK;
+  const int KT2 = (KT + 1) & ~1;                        // (odd KT: the last k-tile of a tile is a phantom tile of zeros, as above)
+  const int grid = (int)gridDim.x;
+
+  auto coords = [&](int vb, int& m0, int& n0, int& grp) {
+    const int wg = sg2_xcd_remap(vb, p.full_tiles);
+    const int mt = wg / n_tiles;
+    m0 = mt * BM;
+    n0 = (wg - mt * n_tiles) * BN;
+    grp = m0 / p.group_rows;
+  };
+  auto bases = [&](int vb, u64& a64, u64& b64, bool& live) {
+    live = vb < p.full_tiles;
+    int m0, n0, grp;
+    coords(live ? vb : 0, m0, n0, grp);
+    a64 = (u64)reinterpret_cast<uintptr_t>(p.a) + (u64)grp * (u64)p.a_group_bytes + 4ull * (u64)(m0 - grp * p.group_rows) * (u64)p.Ca;
+    b64 = (u64)reinterpret_cast<uintptr_t>(p.w) + (u64)grp * (u64)p.w_group_bytes + 4ull * (u64)n0 * (u64)p.Ca;
+  };
+
+  // ---- DMA lane roles: instruction q of wave w covers tile rows (NW q + w) * 8 .. + 7 of BOTH operands; the lane's byte offset
+  // inside a tile does not depend on the tile
+  const int lrow = lane >> 3, lslot = lane & 7;
+  const int r0 = wave * 8 + lrow;
+  const unsigned l_off = 4u * (unsigned)(r0 * p.Ca) + 16u * (unsigned)(lslot ^ ((r0 >> 1) & 7));
+  const unsigned qstride = 4u * (unsigned)(NW * 8 * p.Ca);
+  const unsigned z_off = 16u * (unsigned)lslot;
+  const u64 z_base64 = (u64)reinterpret_cast<uintptr_t>(sg2_zero_page);
+
+  // load cursor: k-tile lk of the tile with sequence index lvb; (nx_*) = the tile after the cursor's
+  int lvb = (int)blockIdx.x, lk = 0;
+  u64 a_cur, b_cur, nx_a, nx_b;
+  bool t_live, nx_live;
+  bases(lvb, a_cur, b_cur, t_live);
+  bases(lvb + grid, nx_a, nx_b, nx_live);
+  bool cur_live = t_live;
+  auto advance = [&]() {
+    ++lk;
+    const bool wrap = lk >= KT2;
+    lk = wrap ? 0 : lk;
+    lvb = wrap ? lvb + grid : lvb;
+    a_cur = wrap ? nx_a : a_cur;
+    b_cur = wrap ? nx_b : b_cur;
+    t_live = wrap ? nx_live : t_live;
+    cur_live = t_live && lk < KT;
+  };
+  auto issue_part = [&](int st, int q) {
+    const u64 kb = (u64)(unsigned)(lk * 128);
+    const u64 sa = cur_live ? a_cur + kb : z_base64;
+    const u64 sb = cur_live ? b_cur + kb : z_base64;
+    const unsigned off = cur_live ? l_off + (unsigned)q * qstride : z_off;
+    const unsigned char* src_a = reinterpret_cast<const unsigned char*>((uintptr_t)(sa + off));
+    const unsigned char* src_b = reinterpret_cast<const unsigned char*>((uintptr_t)(sb + off));
+    unsigned char* dst_a = smem + st * ATILE + (NW * q + wave) * 1024;
+    unsigned char* dst_b = smem + 2 * ATILE + st * BTILE + (NW * q + wave) * 1024;
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src_a, (__attribute__((address_space(3))) void*)dst_a, 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src_b, (__attribute__((address_space(3))) void*)dst_b, 16, 0, 0);
+  };
+
+  f32x16 acc[TM][TN];
+  const int frow = lane & 31, khalf = lane >> 5, swz = (frow >> 1) & 7;
+  const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
+  typedef float v2f __attribute__((ext_vector_type(2)));
+  unsigned a4[8], b4[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    const unsigned ko = 16u * (unsigned)(s ^ swz) + 8u * (unsigned)khalf;
+    a4[s] = lds0 + (unsigned)((wm * (TM * 32) + frow) * 128) + ko;
+    b4[s] = lds0 + (unsigned)(2 * ATILE + (wn * 64 + frow) * 128) + ko;
+  }
+  v2f af4[2][4], bf4[2][2];
+  auto mma4 = [&](int slot) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af4[slot][i][e], bf4[slot][j][e], acc[i][j], 0, 0, 0);
+  };
+  auto mma4_dma = [&](int slot, int st) {
+#pragma unroll
+    for (int e = 0; e < 2; ++e)
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af4[slot][i][e], bf4[slot][j][e], acc[i][j], 0, 0, 0);
+        if (e == 0) {
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int q = i * NQ / TM; q < (i + 1) * NQ / TM; ++q) issue_part(st, q);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+    advance();
+  };
+  // a tile's last k-tile: no DMA behind the barrier (stage `st` becomes the epilogue's staging area); the fragments of the next
+  // tile's first step are read as usual and have landed when the epilogue starts
+#define SG4_K_TILE_LAST(st, sn)                                                              \
+  do {                                                                                       \
+    SG4_STEP(st, 1, 1, 0);                                                                   \
+    SG4_STEP(st, 2, 0, 1);                                                                   \
+    SG4_STEP(st, 3, 1, 0);                                                                   \
+    SG4_STEP(st, 4, 0, 1);                                                                   \
+    SG4_STEP(st, 5, 1, 0);                                                                   \
+    SG4_STEP(st, 6, 0, 1);                                                                   \
+    SG4_STEP(st, 7, 1, 0);                                                                   \
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                              \
+    __builtin_amdgcn_s_barrier();                                                            \
+    SG4_READ_FRAGS(sn, 0, 0);                                                                \
+    __builtin_amdgcn_sched_barrier(0);                                                       \
+    mma4(1);                                                                                 \
+    __builtin_amdgcn_sched_barrier(0);                                                       \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                       \
+    __builtin_amdgcn_sched_barrier(0);                                                       \
+  } while (0)
+
+  // epilogue staging of wave w: bytes [w, w + 1) * 32 KB / NW of (A stage 1 | B stage 1)
+  const int sbyte = wave * (RP * 256);
+  float* stage = reinterpret_cast<float*>(smem + (sbyte < ATILE ? ATILE + sbyte : 2 * ATILE + BTILE + (sbyte - ATILE)));
+  const int c4 = lane & 15, rsub = lane >> 4;
+
+  {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) issue_part(0, q);
+    advance();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) issue_part(1, q);
+    advance();
+    SG4_READ_FRAGS(0, 0, 0);
+  }
+  for (int cvb = (int)blockIdx.x;; cvb += grid) {
+    bases(lvb + grid, nx_a, nx_b, nx_live);            // (the cursor is on this tile, or -- two k-tiles per tile -- already on the next one)
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    for (int kt = 2; kt < KT2; kt += 2) {
+      SG4_K_TILE(0, 1);
+      SG4_K_TILE(1, 0);
+    }
+    SG4_K_TILE(0, 1);                                   // issues k-tile 0 of the next tile (zero page behind the last one)
+    SG4_K_TILE_LAST(1, 0);
+
+    int m0, n0, grp;
+    coords(cvb, m0, n0, grp);
+    float* out_t = p.out + ((size_t)m0 * p.N + n0);
+#pragma unroll
+    for (int ps = 0; ps < 2; ++ps) {
+      constexpr int NR = NW == 4 ? 16 : 8;               // accumulator registers per 32 x 32 block and pass
+      const int i = NW == 4 ? ps : 0, rb = NW == 4 ? 0 : 8 * ps;
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr) stage[((rr & 3) + 8 * (rr >> 2) + 4 * khalf) * 64 + j * 32 + (lane & 31)] = acc[i][j][rb + rr];
+      // (same wave: LDS operations of one wave complete in order)
+#pragma unroll
+      for (int it = 0; it < RP / 4; ++it) {
+        float4 v = *reinterpret_cast<const float4*>(stage + (4 * it + rsub) * 64 + 4 * c4);
+        v.x += 0.f; v.y += 0.f; v.z += 0.f; v.w += 0.f;   // (the one-tile kernel's "+ bias sum" with no bias)
+        const int row = wm * (TM * 32) + ps * RP + 4 * it + rsub;
+        *reinterpret_cast<float4*>(out_t + ((size_t)row * p.N + wn * 64 + 4 * c4)) = v;
+      }
+    }
+    if (cvb + grid >= p.full_tiles) break;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // every wave is done with the staging area (LDS only: the stores stay in flight)
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) issue_part(1, q);
+    advance();
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 // amax of the rows a launch summed with float atomics (reduction-split tail tiles: their final values exist only after the
 // kernel): amax2[0] = max(., max |x|), amax2[1] = max(., max |rowscale[row / rows_per_sample] x|); x [rows, N], N % 4 == 0
 __global__ __launch_bounds__(256) void k_amax_rows(const float* __restrict__ x, long rows, int N, long row0, const float* __restrict__ rowscale,
@@ -714,6 +925,24 @@ __global__ __launch_bounds__(256) void k_amax_rows(const float* __restrict__ x, 
 
 static int g2_split_override = -1;
 extern "C" void sg_debug_set_splitk_v2(int n) { g2_split_override = n; }
+
+// SG_WINO_PERSIST / sg_debug_set_wino_persist: 0 = the one-tile kernel for every grouped fp32 product (the launch of rounds 3-4), 1 = the
+// persistent kernel where it measured ahead (default), 2 = wherever it applies.  SG_WINO_PERSIST_WGS = n > 0 caps its grid (tests: several
+// tiles per workgroup on small problems).
+static int g2_wino_persist = getenv("SG_WINO_PERSIST") ? atoi(getenv("SG_WINO_PERSIST")) : 1;
+static int g2_wino_persist_wgs = getenv("SG_WINO_PERSIST_WGS") ? atoi(getenv("SG_WINO_PERSIST_WGS")) : 0;
+extern "C" void sg_debug_set_wino_persist(int mode, int wgs) {
+  g2_wino_persist = mode;
+  g2_wino_persist_wgs = wgs;
+}
+static bool sg2_wino_persist_wanted(const SgIgemm2Args& a, long M) {
+  if (g2_wino_persist <= 0) return false;
+  // what the persistent kernel leaves out: taps, strides, bias, masks, accumulation, bf16 twins, amax, partly filled tiles
+  if (!a.group_rows || a.ntaps != 1 || a.flags != SG2_IDENT_OUT || !a.out || a.out16 || a.bias || a.bias2 || a.mask || a.mask16 || a.amax_out ||
+      (M % 128) || (a.N % 128) || (a.Ca % 32))
+    return false;
+  return true;
+}
 
 template <int BN, int ES, bool RELU, int BMT = 256, int NWO = 0>
 static int sg2_launch_bn_r(SgIgemm2Args a, hipStream_t s, long* twin_rows_done) {
@@ -754,6 +983,34 @@ static int sg2_launch_bn_r(SgIgemm2Args a, hipStream_t s, long* twin_rows_done) 
   a.full_tiles = full;
   a.tail_split = nsplit;
   a.n_tiles_total = tiles;
+  a.block0 = 0;
+  if constexpr (ES == 4 && BMT == 128 && BN == 128 && !RELU) {
+    // the grouped Winograd-domain products: the full tiles go to the persistent kernel, the reduction-split tail tiles (if any) follow as
+    // a launch of the one-tile kernel that starts at workgroup `full` -- the same tiles, splits and summation orders as the single launch
+    if (full > 0 && sg2_wino_persist_wanted(a, M)) {
+      constexpr int PNW = NWO ? NWO : 4;
+      static bool pattr_done = false;
+      static int slots = 0;
+      if (!pattr_done) {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(sg_wino_persist_kernel<PNW>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 128 * 128) != hipSuccess) {
+          (void)hipGetLastError();
+          return SG_ERR_UNSUPPORTED;
+        }
+        slots = 2 * cus;                       // two workgroups of 64 KB per CU
+        pattr_done = true;
+      }
+      int grid = full < slots ? full : slots;
+      if (g2_wino_persist_wgs > 0 && grid > g2_wino_persist_wgs) grid = g2_wino_persist_wgs;
+      SG_KERNEL((sg_wino_persist_kernel<PNW>), dim3(grid), dim3(PNW * 64), 4 * 128 * 128, s, a);
+      if (full == tiles) {
+        if (twin_rows_done) *twin_rows_done = M;
+        return sg_launch_status();
+      }
+      a.block0 = full;
+    }
+  }
   static bool attr_done = false;
   static const int lds_pad = getenv("SG2_LDS_PAD") ? atoi(getenv("SG2_LDS_PAD")) : 0;      // (occupancy probe: extra bytes requested, never touched)
   const int LDS_BYTES = 2 * BMT * 128 + 2 * BN * 128 + lds_pad;
@@ -764,7 +1021,7 @@ static int sg2_launch_bn_r(SgIgemm2Args a, hipStream_t s, long* twin_rows_done) 
     }
     attr_done = true;
   }
-  SG_KERNEL((sg_igemm_bf16v2_kernel<BN, ES, RELU, BMT, NWO>), dim3(full + (tiles - full) * nsplit), dim3((NWO ? NWO : (BMT == 256 ? 8 : 4)) * 64), LDS_BYTES, s, a);
+  SG_KERNEL((sg_igemm_bf16v2_kernel<BN, ES, RELU, BMT, NWO>), dim3(full - a.block0 + (tiles - full) * nsplit), dim3((NWO ? NWO : (BMT == 256 ? 8 : 4)) * 64), LDS_BYTES, s, a);
   if (twin_rows_done) *twin_rows_done = (a.flags & SG2_IDENT_OUT) ? row0 : (nsplit > 1 ? 0 : M);
   if (a.amax_out && nsplit > 1) {
     // the split tiles' values are final only now: their amax comes from a sweep over those rows (identity layouts: the rows
@@ -784,6 +1041,8 @@ static int sg2_launch_bn(const SgIgemm2Args& a, hipStream_t s, long* twin_rows_d
   else return (a.flags & SG_RELU_IN) ? sg2_launch_bn_r<BN, ES, true, BMT, NWO>(a, s, twin_rows_done) : sg2_launch_bn_r<BN, ES, false, BMT, NWO>(a, s, twin_rows_done);
 }
 
+static int g2_w8 = getenv("SG2_W8") ? atoi(getenv("SG2_W8")) : 1;      // (eight waves per fp32 128 x 128 tile: see the fp32 branch below)
+extern "C" void sg_debug_set_w8(int mode) { g2_w8 = mode; }
 // SG2_TILE128 / sg_debug_set_tile128: 0 = never (default), 1 = the rule below, 2 = whenever the filter count is a multiple of 128
 static int g2_tile128 = getenv("SG2_TILE128") ? atoi(getenv("SG2_TILE128")) : 0;
 extern "C" void sg_debug_set_tile128(int mode) { g2_tile128 = mode; }
@@ -839,7 +1098,7 @@ int sg_launch_igemm_bf16v2(const SgIgemm2Args& a_in, hipStream_t s, long* twin_r
     // shard batch: +8-20 % on its small planes, 34.1 -> 33.3 ms per step (profiles/r04_probe_w8.txt).  On the headline batch the variant is
     // +3 % in isolation but -0.7 % in the two-stream step (its four waves per SIMD hold 492 of the 512 VGPRs: no room for the other
     // network's HBM-bound waves beside it), so large launches keep four waves.  SG2_W8 = 0: never, 2: always.
-    static const int w8 = getenv("SG2_W8") ? atoi(getenv("SG2_W8")) : 1;
+    const int w8 = g2_w8;
     const long g_tiles = (long)sg_cdiv((long)a.Bn * a.Hg * a.Wg, 128) * (a.N / 128);
     if (a.group_rows && a.N % 128 == 0 && (w8 == 2 || (w8 == 1 && g_tiles < 8 * 512))) return sg2_launch_bn<128, 4, 128, 8>(a, s, twin_rows_done);
     if (a.group_rows && a.N % 128) return a.N % 64 == 0 ? sg2_launch_bn<64, 4, 128>(a, s, twin_rows_done) : SG_ERR_UNSUPPORTED;      // (64-filter layers: 128 x 64 tiles, three workgroups per CU)

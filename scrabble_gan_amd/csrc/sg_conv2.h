@@ -31,6 +31,8 @@ struct SgIgemm2Args {
   int group_rows;
   long a_group_bytes, w_group_bytes;
   SgTap taps[SG_MAX_TAPS];   // w_off in elements of the packed filter
+  int block0;                // fp32 128-row tiles only: workgroup b of the launch takes the role of workgroup block0 + b (the reduction-split
+                             // tail tiles as a launch of their own, behind the persistent kernel that computed the full tiles)
 };
 
 // -> SG_OK, and *twin_rows_done = number of leading output rows (pixels) whose bf16 copy the kernel wrote itself; es = bytes per

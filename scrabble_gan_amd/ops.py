@@ -797,6 +797,13 @@ WINO_ROW_GAIN = float(_os.environ.get("SG_WINO_ROW_GAIN", "0.75"))
 WINO_N_MULT = int(_os.environ.get("SG_WINO_N_MULT", "64"))
 
 
+def set_wino_persist(mode: int, wgs: int = 0) -> None:
+    """The grouped products' kernel: 0 = one tile per workgroup, 1 = the persistent tile loop where it measured ahead (default), 2 = wherever
+    it applies; wgs > 0 caps the persistent grid.  The library reads SG_WINO_PERSIST / SG_WINO_PERSIST_WGS when it is loaded; this changes
+    the setting of a running process (tests, probes)."""
+    lib().sg_debug_set_wino_persist(int(mode), int(wgs))
+
+
 def _wino_rows_ok(B, H: int, W: int, tile: int) -> bool:
     if B is None or WINO_ROW_GAIN <= 0 or DETERMINISTIC:       # (deterministic mode: a sample's result must not depend on the batch it rides in)
         return True
