@@ -390,6 +390,32 @@ int sg_image_sheet_u8(const float* imgs, unsigned char* sheet, int N, int H, int
 int sg_augment_fwd(const float* x, const float* params, float* y, float* mean_out, int B, int H, int W, int C, float pad, void* stream);
 int sg_augment_bwd(const float* dy, const float* params, float* dx, int B, int H, int W, int C, void* stream);
 
+/* ---- resampling of a ragged batch of grey uint8 images (scrabble_gan_amd/dinterface.py, data_io.py; csrc/resample.hip; the
+ * reference resizes on the host with cv2.resize: iam_handwriting_db.py:73, data_utils.py:144,179).  ONE launch for the batch.
+ * src: packed source pixels (device, 16-byte aligned); desc [n_img, 8] long on the device, one row per image:
+ *   src_off (bytes, % 16 == 0)  sh  sw  src_stride (bytes per source row, >= sw, % 16 == 0)
+ *   dst_off (output elements; % 4 == 0 for uint8 output)  dh  dw (width the source is resampled to)  canvas_w (width of a written row)
+ * Output row r starts at dst_off + r * canvas_w: columns < min(dw, canvas_w) = the resampled image, columns [dw, canvas_w) = fill
+ * (normalised for fp32 output), columns >= canvas_w of a wider resample are not computed.  1 <= sh, sw <= 32768,
+ * 1 <= dh, dw, canvas_w <= 4096; a row outside these ranges writes nothing.  The bytes between sw and src_stride never reach a result.
+ * Per axis (s -> d pixels), positions and weights from integer arithmetic, each weight rounded to fp32 once, fp32 products and sums,
+ * rows first, ascending taps (bitwise reproducible):
+ *   LINEAR  x = (i + 0.5) s / d - 0.5, taps floor(x), floor(x) + 1 clamped to the image, no anti-aliasing
+ *   CUBIC   the same x, taps floor(x) - 1 .. floor(x) + 2 clamped, Keys kernel with A = -0.75, no anti-aliasing
+ *   AREA    sh >= dh and sw >= dw: box integration of [i s / d, (i + 1) s / d) with fractional coverage at both ends;
+ *           otherwise both axes: taps sx = floor(i s / d), sx + 1, fx = frac((i + 1) - (sx + 1) d / s) (0 when not positive or sx >= s - 1)
+ * These are cv2.resize's definitions as far as they are public; agreement with OpenCV itself is not measured.
+ * SG_ERR_ARG before any launch: n_img < 0, an unknown mode or output kind, fill outside [0, 255], and with n_img > 0 a null or
+ * misaligned pointer (src 16, desc 8, out 4 bytes).  n_img == 0: SG_OK, no launch.  Descriptor contents and buffer extents are
+ * the caller's contract (ops.resample_u8 checks them on the host). */
+#define SG_RESAMPLE_LINEAR 0
+#define SG_RESAMPLE_AREA   1
+#define SG_RESAMPLE_CUBIC  2
+#define SG_RESAMPLE_OUT_U8  0   /* saturate to [0,255], round half to even */
+#define SG_RESAMPLE_OUT_F32 1   /* (v - 127.5) / 127.5, no rounding, no saturation */
+#define SG_RESAMPLE_OUT_F32_QUANT 2   /* the U8 result, then (v - 127.5) / 127.5: bit-identical to OUT_U8 followed by sg_normalize_u8 */
+int sg_resample_u8(const unsigned char* src, const long* desc, int n_img, int mode, int out_kind, void* out, int fill, void* stream);
+
 /* ---- collective of the data-parallel step (the reference has none: BASELINE.json north_star) ----------
  * SUM all-reduce, in place, of `n` elements of a flat device buffer over RCCL on `stream`; gradients are sums over the
  * batch (reference data_utils.py:450,454,458,467 differentiate [B,1] targets), so ranks ADD.  comm = the ncclComm_t made by

@@ -1,12 +1,14 @@
 """Entry point with the reference's configurable surface (/root/reference/src/main.py):
 setup_optimizer :25-35, shared_specs (get_shared_specs) :38-40, io (setup_io) :43-51 and main() :54-116.
 
-    python -m scrabble_gan_amd.main --gin configs/scrabble_gan_mi355x.gin [--synthetic] [--steps N]
+    python -m scrabble_gan_amd.main --gin configs/scrabble_gan_mi355x.gin [--synthetic | --raw-words [DIR]] [--steps N]
 
 `--synthetic` swaps the IAM bucket folders (absent offline) for the synthetic generators of
 SURVEY section 8(d); everything downstream (factories, optimizers, train loop) is the same code.
+`--raw-words [DIR]` trains on the unconverted IAM word crops (data_io.RawWordCorpus: every batch is resampled on the GPU);
+`python -m scrabble_gan_amd.prepare_data` writes the bucket folders the default path reads (dinterface.py).
 `--ema-decay D` keeps an averaged generator (averaging.py), `--samples-every N` writes the reference's per-epoch picture
-image_at_epoch_NNNN.png, `--augment color,translation,cutout` shows D augmented images only (augment.py).  The dataset conversion (dinterface) and GIF writer of the reference are out of scope."""
+image_at_epoch_NNNN.png, `--augment color,translation,cutout` shows D augmented images only (augment.py).  The GIF writer of the reference is out of scope."""
 from __future__ import annotations
 
 import argparse
@@ -84,6 +86,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--gin", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "configs",
                                                   "scrabble_gan_mi355x.gin"))
     ap.add_argument("--synthetic", action="store_true")
+    ap.add_argument("--raw-words", nargs="?", const=True, default=None, metavar="DIR",
+                    help="train on the unconverted IAM word crops under DIR (default: io.raw_dir), resampled per batch on the GPU; "
+                         "words.txt is <DIR>/../gt/words.txt")
+    ap.add_argument("--style-dir", default=None, help="folder of the free-size style crops (default: load_style_input's)")
     ap.add_argument("--resumable", action="store_true",
                     help="write the full training state to <checkpoints>/state/latest.safetensors every epoch and resume from it when it exists")
     ap.add_argument("--conv-dtype", default="f32", choices=["f32", "bf16"], help="matrix-core operand type of the convolutions")
@@ -117,6 +123,8 @@ def main(argv=None):
         ap.error("--ema-decay must be in [0, 1)")
     if min(args.ema_start, args.ema_standing_batches, args.samples_every) < 0:
         ap.error("--ema-start, --ema-standing-batches and --samples-every must be >= 0")
+    if args.synthetic and args.raw_words is not None:
+        ap.error("--synthetic and --raw-words are mutually exclusive")
     if args.ema_standing_batches and not args.ema_decay:
         ap.error("--ema-standing-batches needs --ema-decay")
     augment = ""
@@ -146,15 +154,25 @@ def main(argv=None):
         random_words = synthetic_random_words(bucket_size, 1000, n_classes)
         train_dataset = synthetic_dataset(batch_size, in_dim, bucket_size, n_classes)
         train_imgs = [synthetic_batch(1, 10, in_dim, n_classes, seed=1000 + i)[2][0] for i in range(64)]
+    elif args.raw_words is not None:
+        from .data_io import RawWordCorpus, load_style_input
+        from .net_architecture import _device
+        if args.raw_words is not True:
+            raw_dir = args.raw_words
+        train_dataset = RawWordCorpus(raw_dir, None, char_vec, bucket_size, in_dim, _device(), batch_size=batch_size)
+        random_words = train_dataset.random_words()
+        style = {"style_dir": args.style_dir} if args.style_dir else {}
+        train_imgs, _ = load_style_input(in_dim, batch_size, bucket_size, resample="device", **style)
     else:
         if not os.path.exists(read_dir):
-            raise FileNotFoundError("%s not found: the IAM conversion (dinterface) is out of scope; use --synthetic" % read_dir)
+            raise FileNotFoundError("%s not found: write it with `python -m scrabble_gan_amd.prepare_data` (the IAM conversion), train on "
+                                    "the raw word crops with --raw-words, or use --synthetic" % read_dir)
         from .data_io import DevicePrefetcher, load_prepare_data, load_style_input      # "next" tier
         from .net_architecture import _device
         random_words = load_random_word_list(read_dir, bucket_size, char_vec)
         # uint8 pixels staged in pinned memory by a background thread, copied asynchronously, normalised on the GPU
         train_dataset = DevicePrefetcher(load_prepare_data(in_dim, batch_size, read_dir, char_vec, bucket_size, raw=True), _device())
-        train_imgs, _ = load_style_input(in_dim, batch_size, bucket_size)
+        train_imgs, _ = load_style_input(in_dim, batch_size, bucket_size, **({"style_dir": args.style_dir} if args.style_dir else {}))
 
     generator, discriminator, recognizer, style_promoter, gan = build_models(
         in_dim, latent_dim, embed_y, kernel_reg, g_bw_attention, d_bw_attention, n_classes, seq_len, my_rec, my_disc,

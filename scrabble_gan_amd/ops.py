@@ -1247,6 +1247,109 @@ def normalize_u8(u8: torch.Tensor) -> torch.Tensor:
     return out
 
 
+RESAMPLE_LINEAR, RESAMPLE_AREA, RESAMPLE_CUBIC = 0, 1, 2
+RESAMPLE_OUT_U8, RESAMPLE_OUT_F32, RESAMPLE_OUT_F32_QUANT = 0, 1, 2
+RESAMPLE_MAX_SRC, RESAMPLE_MAX_DST = 32768, 4096
+
+
+def pack_gray_images(images, pin: Optional[bool] = None):
+    """[uint8 [h, w] arrays] -> (flat uint8 tensor, offsets int64 [n], strides int64 [n]) in sg_resample_u8's source layout: every
+    row starts a multiple of 16 bytes from the start of the buffer (stride = w rounded up to 16, padding zero), so every image
+    does too.  The buffer is pinned when a GPU is there (pin=None) so that its upload can be asynchronous."""
+    import numpy as np
+    n = len(images)
+    strides = np.array([(int(im.shape[1]) + 15) & ~15 for im in images], np.int64).reshape(n)
+    sizes = np.array([int(im.shape[0]) for im in images], np.int64).reshape(n) * strides
+    offsets = np.zeros(n, np.int64)
+    if n > 1:
+        offsets[1:] = np.cumsum(sizes)[:-1]
+    total = int(sizes.sum())
+    pin = torch.cuda.is_available() if pin is None else pin
+    buf = torch.zeros(max(total, 16), dtype=torch.uint8, pin_memory=bool(pin))
+    flat = buf.numpy()
+    for im, off, st in zip(images, offsets, strides):
+        if im.dtype != np.uint8 or im.ndim != 2 or im.shape[0] < 1 or im.shape[1] < 1:
+            raise ValueError("pack_gray_images takes non-empty 2-D uint8 arrays, got %s %s" % (im.dtype, im.shape))
+        h, w = im.shape
+        flat[off:off + h * st].reshape(h, st)[:, :w] = im
+    return buf, offsets, strides
+
+
+def resample_desc(offsets, strides, src_shapes, dst_offsets, dh, dw, canvas_w):
+    """The [n, 8] int64 descriptor table of sg_resample_u8 from per-image columns (scalars broadcast)."""
+    import numpy as np
+    n = len(offsets)
+    src_shapes = np.asarray(src_shapes, np.int64).reshape(n, 2)
+    desc = np.empty((n, 8), np.int64)
+    desc[:, 0], desc[:, 1], desc[:, 2], desc[:, 3] = offsets, src_shapes[:, 0], src_shapes[:, 1], strides
+    desc[:, 4], desc[:, 5], desc[:, 6], desc[:, 7] = dst_offsets, dh, dw, canvas_w
+    return desc
+
+
+def check_resample_desc(desc, src_bytes: int, out_elems: Optional[int], out_kind: int):
+    """Host-side validation of a descriptor table (the device cannot check it without a synchronisation): alignment, ranges, source
+    extents, output extents and output regions that do not overlap.  -> (desc as int64 [n, 8], output elements the table needs)."""
+    import numpy as np
+    d = np.ascontiguousarray(np.asarray(desc, dtype=np.int64))
+    if d.ndim != 2 or d.shape[1] != 8:
+        raise ValueError("descriptor table must be [n_img, 8], got %s" % (d.shape,))
+    if d.shape[0] == 0:
+        return d, 0
+    so, sh, sw, st, do, dh, dw, cw = (d[:, k] for k in range(8))
+    if (so < 0).any() or (so % 16).any():
+        raise ValueError("src_off must be a non-negative multiple of 16")
+    if (st < sw).any() or (st % 16).any():
+        raise ValueError("src_stride must be at least sw and a multiple of 16")
+    if (np.minimum(sh, sw) < 1).any() or (np.maximum(sh, sw) > RESAMPLE_MAX_SRC).any():
+        raise ValueError("source sizes must be in [1, %d]" % RESAMPLE_MAX_SRC)
+    if (np.minimum(np.minimum(dh, dw), cw) < 1).any() or (np.maximum(np.maximum(dh, dw), cw) > RESAMPLE_MAX_DST).any():
+        raise ValueError("dh, dw and canvas_w must be in [1, %d]" % RESAMPLE_MAX_DST)
+    if ((so + sh * st) > src_bytes).any():
+        raise ValueError("a source image ends past the source buffer (%d bytes)" % src_bytes)
+    if (do < 0).any() or (out_kind == RESAMPLE_OUT_U8 and (do % 4).any()):
+        raise ValueError("dst_off must be non-negative, and a multiple of 4 for uint8 output")
+    end = do + dh * cw
+    order = np.argsort(do, kind="stable")
+    if (do[order][1:] < end[order][:-1]).any():
+        raise ValueError("output regions overlap")
+    need = int(end.max())
+    if out_elems is not None and need > out_elems:
+        raise ValueError("an output region ends past the output buffer (%d elements)" % out_elems)
+    return d, need
+
+
+def resample_u8(src_u8: torch.Tensor, desc, mode: int, out_kind: int, out: Optional[torch.Tensor] = None, fill: int = 255) -> torch.Tensor:
+    """One sg_resample_u8 launch on the current stream for a ragged batch of grey images.  src_u8: flat uint8 source buffer
+    (pack_gray_images' layout) on the device, or on the host (copied asynchronously when it is pinned); desc: HOST table [n, 8]
+    (resample_desc), validated here and uploaded.  -> the flat output (uint8 or fp32), `out` when given."""
+    if mode not in (RESAMPLE_LINEAR, RESAMPLE_AREA, RESAMPLE_CUBIC) or out_kind not in (RESAMPLE_OUT_U8, RESAMPLE_OUT_F32, RESAMPLE_OUT_F32_QUANT):
+        raise ValueError("unknown resample mode %r / output kind %r" % (mode, out_kind))
+    if not 0 <= int(fill) <= 255:
+        raise ValueError("fill must be in [0, 255]")
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 1 or not src_u8.is_contiguous():
+        raise ValueError("src_u8 must be a flat contiguous uint8 tensor")
+    want = torch.uint8 if out_kind == RESAMPLE_OUT_U8 else torch.float32
+    if out is not None and not (out.is_cuda and out.is_contiguous() and out.dtype == want):
+        raise ValueError("out must be a contiguous %s CUDA tensor" % want)
+    d, need = check_resample_desc(desc, src_u8.numel(), None if out is None else out.numel(), out_kind)
+    device = src_u8.device if src_u8.is_cuda else (out.device if out is not None else torch.device("cuda", torch.cuda.current_device()))
+    if not src_u8.is_cuda:
+        src_u8 = src_u8.to(device, non_blocking=True)
+    if src_u8.data_ptr() % 16:
+        raise ValueError("the source buffer must be 16-byte aligned")
+    if out is None:
+        out = torch.empty((need + 3) & ~3, device=device, dtype=want)
+    n = d.shape[0]
+    if n == 0:
+        return out
+    host = torch.empty((n, 8), dtype=torch.int64, pin_memory=True)
+    host.copy_(torch.from_numpy(d))
+    ddev = host.to(device, non_blocking=True)
+    with _hbm("resample", src_u8, out):
+        call("sg_resample_u8", src_u8.data_ptr(), ddev.data_ptr(), n, int(mode), int(out_kind), out.data_ptr(), int(fill), _stream())
+    return out
+
+
 def bias_add(y, bias):
     """y[..., c] += bias[c] in place."""
     _chk(y, bias)
