@@ -416,6 +416,28 @@ int sg_augment_bwd(const float* dy, const float* params, float* dx, int B, int H
 #define SG_RESAMPLE_OUT_F32_QUANT 2   /* the U8 result, then (v - 127.5) / 127.5: bit-identical to OUT_U8 followed by sg_normalize_u8 */
 int sg_resample_u8(const unsigned char* src, const long* desc, int n_img, int mode, int out_kind, void* out, int fill, void* stream);
 
+/* ---- fidelity statistics of feature rows (scrabble_gan_amd/fidelity.py; csrc/fidelity.hip; not in the reference, which
+ * reports FID from a separate script): the streaming moments behind the Frechet distance and the polynomial-kernel Gram sums
+ * behind the kernel distance (KID).  Features are fp32, every result is fp64.  Both products run on the fp64 matrix cores with
+ * the fp32 operands widened on their way into the fragments: a product of two fp32 values is exact in fp64, so the only
+ * rounding is the order of the additions, and that order is fixed -- no floating-point atomics, one workgroup per output tile,
+ * partial sums added in index order.  Two calls on the same inputs give bitwise equal outputs.
+ * sg_feature_moments: sum [D] += sum_i x[i,:], outer [D,D] += sum_i x[i,:]^T x[i,:] for x [n, ldx >= D], n >= 1, 1 <= D <= 4096.
+ *   Additive over calls (and over ranks): the caller zeroes both once.  Only tile pairs on or above the diagonal are computed; the
+ *   owner of a tile stores it and its transpose, so outer is bitwise symmetric.
+ * sg_feature_cov: mean = sum / count, cov = (outer - count mean mean^T) / (count - 1), count >= 2; four distinct buffers.
+ * sg_poly_mmd_sums: for each subset s < S with rows X_i = x[ix[s,i]], Y_j = y[iy[s,j]] (ix / iy int32 [S,m]; NULL = rows 0..m-1 for
+ *   every s): sums[s] = { sum_{i!=j} k(X_i,X_j), sum_{i!=j} k(Y_i,Y_j), sum_{i,j} k(X_i,Y_j) }, k(a,b) = (gamma a.b + coef0)^3, fp64 [S,3],
+ *   OVERWRITTEN.  m >= 1 (m == 1: the first two sums are 0), 1 <= D <= 4096, ldx, ldy >= D.  workspace:
+ *   sg_poly_mmd_workspace_doubles(S, m) doubles of scratch (one partial sum per 64x64 tile; -1 for S < 1 or m < 1).  Row indices
+ *   out of range are the caller's responsibility (fidelity.draw_subsets builds and checks them on the host).
+ * SG_ERR_ARG before any launch: a null required pointer or a size outside the ranges above. */
+int sg_feature_moments(const float* x, long ldx, int n, int D, double* sum, double* outer, void* stream);
+int sg_feature_cov(const double* sum, const double* outer, double count, double* mean, double* cov, int D, void* stream);
+long sg_poly_mmd_workspace_doubles(int S, int m);
+int sg_poly_mmd_sums(const float* x, long ldx, const float* y, long ldy, const int* ix, const int* iy, int S, int m, int D,
+                     double gamma, double coef0, double* workspace, double* sums, void* stream);
+
 /* ---- collective of the data-parallel step (the reference has none: BASELINE.json north_star) ----------
  * SUM all-reduce, in place, of `n` elements of a flat device buffer over RCCL on `stream`; gradients are sums over the
  * batch (reference data_utils.py:450,454,458,467 differentiate [B,1] targets), so ranks ADD.  comm = the ncclComm_t made by

@@ -498,7 +498,8 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
           generator_optimizer, discriminator_optimizer, recognizer_optimizer, stylepromoter_optimizer, my_imgs,
           seed_labels, buffer_size, batch_size, epochs, model_path, latent_dim, gen_path, loss_fn, disc_iters,
           apply_gradient_balance, random_words, bucket_size, char_vector, max_batches_per_epoch=None, state_path=None,
-          ema_decay=0.0, ema_start=0, ema_standing_batches=0, samples_every=0, augment="", augment_p=1.0, legibility_every=0):
+          ema_decay=0.0, ema_start=0, ema_standing_batches=0, samples_every=0, fidelity_every=0, fidelity_real_batches=8, fidelity_samples=256,
+          augment="", augment_p=1.0, legibility_every=0):
     """Epoch/batch loop, 16-column ';' summaries and per-epoch G/R weight saves (data_utils.py:198-352).
     The summary rows carry the ';' the reference drops between g_loss_std and s_loss (Appendix C-10).
     `state_path` (not in the reference): full training state written there after every epoch and, when the file exists
@@ -522,6 +523,11 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
     augment.DiffAugment -- D then sees only augmented images, real and generated, each family applied with probability `augment_p`
     (train_step's `augment`).  The sampler has its own random stream; the full state (`state_path`) then carries the run's random
     streams and the sampler's (`rng/augment`), and a resumed run skips the batches of the finished epochs, as with an average.
+    `fidelity_every` = N > 0 (not in the reference): after every Nth epoch one line `epoch,n_real,n_fake,frechet,kid,kid_std` is appended
+    to <model_path>/fidelity.csv (fidelity_ema.csv for the averaged generator when there is one): Frechet and kernel distance, in the
+    recognizer's feature space (fidelity.py), between the first `fidelity_real_batches` training batches of the run -- kept as images,
+    so that the recognizer of the moment sees both sets -- and G's inference rendering of `fidelity_samples` words, drawn once from a
+    generator of the hook's own.  Nothing is drawn from the streams training uses.  Rank 0 evaluates, as with `legibility_every`.
     With all of these at their defaults nothing is launched, drawn or written that was not before."""
     generator_save_dir = os.path.join(checkpoint_prefix, 'generator/')
     recognizer_save_dir = os.path.join(checkpoint_prefix, 'recognizer/')
@@ -550,6 +556,10 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
     if augment:
         from .augment import DiffAugment
         aug = augment if isinstance(augment, DiffAugment) else DiffAugment(augment, p=augment_p)
+    fid = None
+    if fidelity_every > 0 and is_main:
+        from .fidelity import EpochFidelity
+        fid = EpochFidelity(random_words, my_imgs, batch_size, real_batches=fidelity_real_batches, samples=fidelity_samples)
     exact = avg is not None or aug is not None               # the state carries the random streams and a resumed run replays the dataset
     if state_path is not None and os.path.exists(state_path):
         if exact:
@@ -584,6 +594,8 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
             for batch_idx in range(batch_per_epoch):
                 image_batch, label_batch = next(dataset)
                 my_img_batch = random.choices(my_imgs, k=batch_size)
+                if fid is not None:
+                    fid.observe(image_batch)
                 fake_labels = None
                 if legibility_every > 0 and (epoch_idx + 1) % legibility_every == 0 and batch_idx == batch_per_epoch - 1:
                     # the evaluation below needs this step's fake labels: train_step's own draw (and rank-0 broadcast), made here
@@ -619,6 +631,9 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
                         f.write(LEGIBILITY_HEADER)
                     f.write(",".join(str(v) for v in (epoch_idx + 1, leg["n"], leg["cer_real"], leg["wer_real"], leg["cer_fake"],
                                                       leg["wer_fake"])) + "\n")
+            if fid is not None and (epoch_idx + 1) % fidelity_every == 0:
+                from .fidelity import append_csv
+                append_csv(os.path.join(model_path, "fidelity.csv"), epoch_idx + 1, fid.evaluate(generator, recognizer))
             generator.save_weights(os.path.join(generator_save_dir, str(epoch_idx + 1), 'cktp-' + str(epoch_idx + 1)))
             recognizer.save_weights(os.path.join(recognizer_save_dir, str(epoch_idx + 1), 'cktp-' + str(epoch_idx + 1)))
             if avg is not None:
@@ -635,6 +650,10 @@ def train(dataset, generator, discriminator, recognizer, style_promoter, composi
                             f.write(LEGIBILITY_HEADER)
                         f.write(",".join(str(v) for v in (epoch_idx + 1, leg["n"], leg["cer_real"], leg["wer_real"], leg["cer_fake"],
                                                           leg["wer_fake"])) + "\n")
+                if fid is not None and (epoch_idx + 1) % fidelity_every == 0:
+                    from .fidelity import append_csv
+                    with avg.applied():
+                        append_csv(os.path.join(model_path, "fidelity_ema.csv"), epoch_idx + 1, fid.evaluate(generator, recognizer))
             if samples_every > 0 and (epoch_idx + 1) % samples_every == 0:
                 _save_sample_sheet(generator, avg, my_imgs, seed_labels[1], os.path.join(gen_path, 'image_at_epoch_{:04d}.png'.format(epoch_idx + 1)))
             if state_path is not None:

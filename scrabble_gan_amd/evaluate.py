@@ -3,12 +3,23 @@
     python -m scrabble_gan_amd.evaluate --recognizer-weights run/checkpoints/recognizer/15/cktp-15 [--my-rec] \
         (--data DIR | --synthetic) [--batches 20] [--batch-size 64] [--lexicon words.txt] \
         [--generator-weights run/checkpoints/generator/15/cktp-15 --words machine learning]
+        [--fidelity 10000 [--feature-space recognizer|discriminator] [--discriminator-weights PREFIX] [--real-stats real.npz]
+         [--kid-subsets 100] [--kid-subset-size 1000]]
+    python -m scrabble_gan_amd.evaluate --features-real A.npy --features-fake B.npy
 
 `--data DIR` is the bucket-folder layout the train loop reads (<DIR>/<L>/<name>.png + .txt); `--synthetic` takes the
 uniform-noise batches of `main.py --synthetic` (no dataset at hand: the rates then only show that the path runs).
 With `--lexicon FILE` (one word per line) every image is also read as the lexicon word of lowest CTC cost.  With
 `--generator-weights` each of `--words` is rendered in inference mode and read back.  Prints ONE JSON line:
-{cer, wer, n_words, n_chars[, cer_lexicon, wer_lexicon][, read_back: [{target, read, distance}], cer_fake, wer_fake]}."""
+{cer, wer, n_words, n_chars[, cer_lexicon, wer_lexicon][, read_back: [{target, read, distance}], cer_fake, wer_fake]
+ [, frechet, kid, kid_std, n_real, n_fake, feature_space, dim]}.
+
+`--fidelity N` (with `--generator-weights`) renders N words -- drawn from `--lexicon`, else from the labels of the real batches --
+and reports the Frechet and kernel distances (fidelity.py) between the real batches and the renderings in the feature space of
+the recognizer (default) or of a discriminator (`--discriminator-weights`).  THESE NUMBERS ARE NOT COMPARABLE WITH INCEPTION-BASED
+FID / KID.  `--real-stats FILE.npz`: the real set's statistics are read from FILE if it exists (the Frechet distance then uses
+them) and written there otherwise.  `--features-real A.npy --features-fake B.npy` applies the same formulas to two precomputed
+[N,D] feature arrays (exported Inception pool3 features, say) and needs no network."""
 from __future__ import annotations
 
 import argparse
@@ -22,9 +33,9 @@ CHAR_VEC = 'abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ'
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--recognizer-weights", required=True, help="checkpoint prefix (without .safetensors)")
+    ap.add_argument("--recognizer-weights", default=None, help="checkpoint prefix (without .safetensors)")
     ap.add_argument("--my-rec", action="store_true", help="the BiLSTM recognizer (make_my_recognizer)")
-    src = ap.add_mutually_exclusive_group(required=True)
+    src = ap.add_mutually_exclusive_group()
     src.add_argument("--data", default=None, metavar="DIR", help="bucket folders <DIR>/<L>/<name>.png + .txt")
     src.add_argument("--synthetic", action="store_true", help="synthetic batches (no dataset at hand)")
     ap.add_argument("--batches", type=int, default=20)
@@ -35,7 +46,30 @@ def parse_args(argv=None):
     ap.add_argument("--words", nargs="+", default=["machine", "learning"])
     ap.add_argument("--char-vec", default=CHAR_VEC)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--fidelity", type=int, default=0, metavar="N", help="render N words and report Frechet / kernel distances to the real batches")
+    ap.add_argument("--feature-space", default="recognizer", choices=["recognizer", "discriminator"])
+    ap.add_argument("--discriminator-weights", default=None, help="discriminator checkpoint prefix (--feature-space discriminator)")
+    ap.add_argument("--real-stats", default=None, metavar="FILE.npz", help="the real set's statistics: read if present, written otherwise")
+    ap.add_argument("--kid-subsets", type=int, default=100)
+    ap.add_argument("--kid-subset-size", type=int, default=1000)
+    ap.add_argument("--features-real", default=None, metavar="A.npy", help="precomputed real features [N,D]: no networks needed")
+    ap.add_argument("--features-fake", default=None, metavar="B.npy")
     args = ap.parse_args(argv)
+    if (args.features_real is None) != (args.features_fake is None):
+        ap.error("--features-real and --features-fake go together")
+    if args.kid_subsets < 1 or args.kid_subset_size < 2:
+        ap.error("--kid-subsets must be >= 1 and --kid-subset-size >= 2")
+    if args.features_real is None:
+        if args.recognizer_weights is None:
+            ap.error("--recognizer-weights is required")
+        if args.data is None and not args.synthetic:
+            ap.error("one of --data / --synthetic is required")
+    if args.fidelity < 0 or args.fidelity == 1:
+        ap.error("--fidelity needs at least 2 words")
+    if args.fidelity and not args.generator_weights:
+        ap.error("--fidelity needs --generator-weights")
+    if args.fidelity and args.feature_space == "discriminator" and not args.discriminator_weights:
+        ap.error("--feature-space discriminator needs --discriminator-weights")
     if args.batches < 1 or args.batch_size < 1:
         ap.error("--batches and --batch-size must be positive")
     return args
@@ -60,6 +94,12 @@ def read_lexicon(path, char_vec):
 def main(argv=None):
     args = parse_args(argv)
     import torch
+    if args.features_real is not None:
+        from . import fidelity
+        out = fidelity.fidelity_from_features(np.load(args.features_real), np.load(args.features_fake), args.kid_subsets,
+                                              args.kid_subset_size, device=args.device)
+        print(json.dumps(out))
+        return out
     from . import legibility, net_architecture as NA
     NA.configure(device=torch.device(args.device))
     in_dim, n_classes = (32, 160, 1), len(args.char_vec)
@@ -73,7 +113,8 @@ def main(argv=None):
         from .data_io import load_prepare_data
         dataset = load_prepare_data(in_dim, args.batch_size, args.data.rstrip("/") + "/", args.char_vec, args.bucket_size)
     lexicon = read_lexicon(args.lexicon, args.char_vec) if args.lexicon else None
-    out = legibility.evaluate_recognizer(R, itertools.islice(dataset, args.batches), args.char_vec, lexicon)
+    batches = list(itertools.islice(dataset, args.batches))
+    out = legibility.evaluate_recognizer(R, batches, args.char_vec, lexicon)
     if args.generator_weights:
         G = NA.make_generator(128, in_dim, (32, 8192), None, "B3", n_classes, vis_model=False)
         G.load_weights(args.generator_weights)
@@ -82,8 +123,42 @@ def main(argv=None):
         out["read_back"] = rb
         out["cer_fake"] = sum(r["distance"] for r in rb) / max(1, sum(len(r["target"]) for r in rb))
         out["wer_fake"] = sum(r["distance"] != 0 for r in rb) / len(rb)
+    if args.fidelity:
+        out.update(_fidelity(args, NA, G, R, batches, lexicon, in_dim))
     print(json.dumps(out))
     return out
+
+
+def _fidelity(args, NA, G, R, batches, lexicon, in_dim):
+    """--fidelity: N words from the lexicon (or from the real batches' labels) rendered in random styles, against `batches`."""
+    import os
+    from . import fidelity
+    longest = max(max(len(w) for w in lexicon), 1) if lexicon else max(np.asarray(lab).shape[1] for _, lab in batches)
+    buckets = [[] for _ in range(longest)]
+    if lexicon:
+        for w in lexicon:
+            buckets[len(w) - 1].append([args.char_vec.index(c) for c in w])
+    else:
+        for _, lab in batches:
+            lab = np.asarray(lab.cpu() if hasattr(lab, "cpu") else lab)
+            buckets[lab.shape[1] - 1] += [list(map(int, row)) for row in lab]
+    model = R
+    if args.feature_space == "discriminator":
+        model = NA.make_discriminator(in_dim, None, "B1", vis_model=False)
+        model.load_weights(args.discriminator_weights)
+    stats = None
+    if args.real_stats:
+        dim = fidelity.FeatureExtractor(model, args.feature_space).dim
+        stats = (fidelity.FeatureStats.load(args.real_stats, model.device) if os.path.exists(args.real_stats)
+                 else fidelity.FeatureStats(dim, model.device))
+    fresh = stats is not None and stats.n == 0
+    style = np.random.default_rng(0).uniform(-1, 1, (16,) + tuple(in_dim)).astype(np.float32)
+    res = fidelity.evaluate_fidelity(G, model, batches, style, fidelity.fake_word_batches(buckets, args.fidelity, args.batch_size),
+                                     space=args.feature_space, real_stats=stats, subsets=args.kid_subsets,
+                                     subset_size=args.kid_subset_size)
+    if fresh:
+        stats.save(args.real_stats)
+    return res
 
 
 if __name__ == "__main__":

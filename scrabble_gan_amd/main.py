@@ -101,6 +101,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="no float-atomic reduction splits in the conv kernels: bitwise reproducible runs, a few percent slower")
     ap.add_argument("--legibility-every", type=int, default=0,
                     help="after every Nth epoch append R's character / word error rates on real and generated words to <model_dir>/legibility.csv")
+    ap.add_argument("--fidelity-every", type=int, default=0,
+                    help="after every Nth epoch append the Frechet and kernel distances between real and generated words, in the recognizer's "
+                         "feature space (not comparable with Inception-based FID / KID), to <model_dir>/fidelity.csv")
+    ap.add_argument("--fidelity-real-batches", type=int, default=8, help="--fidelity-every: the run's first training batches kept as the real set")
+    ap.add_argument("--fidelity-samples", type=int, default=256, help="--fidelity-every: generated words per evaluation")
     ap.add_argument("--ema-decay", type=float, default=0.0,
                     help="> 0: keep an exponential moving average of the generator's weights (e.g. 0.9999) and write it per epoch to "
                          "<checkpoints>/generator_ema/<e>/cktp-<e>; 0 (default): off")
@@ -123,6 +128,8 @@ def main(argv=None):
         ap.error("--ema-decay must be in [0, 1)")
     if min(args.ema_start, args.ema_standing_batches, args.samples_every) < 0:
         ap.error("--ema-start, --ema-standing-batches and --samples-every must be >= 0")
+    if args.fidelity_every < 0 or args.fidelity_real_batches < 1 or args.fidelity_samples < 2:
+        ap.error("--fidelity-every must be >= 0, --fidelity-real-batches >= 1 and --fidelity-samples >= 2")
     if args.synthetic and args.raw_words is not None:
         ap.error("--synthetic and --raw-words are mutually exclusive")
     if args.ema_standing_batches and not args.ema_decay:
@@ -188,7 +195,8 @@ def main(argv=None):
           max_batches_per_epoch=args.steps,
           state_path=os.path.join(ckpt_path, "state", "latest.safetensors") if args.resumable else None,
           legibility_every=args.legibility_every, ema_decay=args.ema_decay, ema_start=args.ema_start,
-          ema_standing_batches=args.ema_standing_batches, samples_every=args.samples_every, augment=augment)
+          ema_standing_batches=args.ema_standing_batches, samples_every=args.samples_every, augment=augment,
+          fidelity_every=args.fidelity_every, fidelity_real_batches=args.fidelity_real_batches, fidelity_samples=args.fidelity_samples)
 
 
 if __name__ == "__main__":

@@ -275,6 +275,11 @@ class DiscriminatorModel(_Model):
         logits = ops.dense_fwd(h, S.p["dense.w"])                              # [B,1]
         return logits, (tctx, h, S)
 
+    def features(self, x, nl=None):
+        """fp32 [B, 1024]: the trunk's pooled `h`, the vector the Dense layer reads.  In nl_mode 'reference' the NonLocalBlock
+        kernels are drawn from `nl_gen` on every call unless `nl` gives them: a metric passes one fixed set (fidelity.py)."""
+        return self.forward(x, nl)[1][1]
+
     def forward_multi(self, xs, nls):
         """Several reference calls of this model (same input width) as ONE pass over the concatenated batch: the
         nets have no BatchNorm, so samples are independent and the result equals separate calls; only the
@@ -536,6 +541,15 @@ class RecognizerModel(_Model):
         training=False BatchNorm uses its moving statistics and nothing in the model changes."""
         with ops.bf16_only():
             return self._trunk(x, bool(training and self.trainable))[0]
+
+    def features(self, x):
+        """fp32 [B, C]: the mean over the T frames of the per-frame feature the Dense layer reads (C = 512; 512 for the BiLSTM
+        recognizer too), so words of every length land in one space (fidelity.py).  Inference mode: BatchNorm moving statistics,
+        no dropout masks, nothing in the model changes."""
+        with ops.bf16_only():
+            out = self._trunk(_as_nhwc1(x, self.device), False)
+        feat, (B, T) = out[-2], out[-1]
+        return ops.gap_fwd(feat.contiguous().view(B, 1, T, feat.shape[1]), relu=False)
 
     def transcribe(self, x, input_length=None):
         """Best-path reading of the first `input_length` frames (default: the 4L-1 the CTC head trains on) -> (labels int32 [B,input_length] with -1

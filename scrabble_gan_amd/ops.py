@@ -1675,6 +1675,87 @@ def legibility_sums(dist, ref_len, sums=None):
     return sums
 
 
+# ---------------------------------------------------------------- fidelity statistics (csrc/fidelity.hip)
+MAX_FEATURE_DIM = 4096
+
+
+def _chk_f64(name: str, t, shape):
+    if not (torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 and tuple(t.shape) == tuple(shape)):
+        raise ValueError("%s must be a contiguous fp64 CUDA tensor of shape %s" % (name, tuple(shape)))
+
+
+def _chk_rows(name: str, x):
+    """fp32 CUDA rows [n, D] whose columns are contiguous (a column slice of a wider tensor is fine) -> (n, D, row stride)."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
+        raise ValueError("%s must be an fp32 CUDA tensor [n, D]" % name)
+    n, D = x.shape
+    if n < 1 or not (1 <= D <= MAX_FEATURE_DIM):
+        raise ValueError("%s %s: n >= 1 and 1 <= D <= %d" % (name, tuple(x.shape), MAX_FEATURE_DIM))
+    ld = x.stride(0) if n > 1 else max(x.stride(0), D)
+    if (D > 1 and x.stride(1) != 1) or ld < D:
+        raise ValueError("%s: columns must be contiguous and rows at least D apart (strides %s)" % (name, tuple(x.stride())))
+    return n, D, ld
+
+
+def feature_moments(x, sum=None, outer=None):
+    """sum fp64 [D] += sum_i x[i], outer fp64 [D,D] += sum_i x[i]^T x[i] for fp32 rows x [n,D]; zeroed buffers are made when none
+    are given.  Additive over calls; outer stays bitwise symmetric.  -> (sum, outer)"""
+    n, D, ld = _chk_rows("feature_moments: x", x)
+    if (sum is None) != (outer is None):
+        raise ValueError("feature_moments: give both sum and outer, or neither")
+    if sum is None:
+        sum = torch.zeros(D, device=x.device, dtype=torch.float64)
+        outer = torch.zeros(D, D, device=x.device, dtype=torch.float64)
+    _chk_f64("feature_moments: sum", sum, (D,))
+    _chk_f64("feature_moments: outer", outer, (D, D))
+    call("sg_feature_moments", x.data_ptr(), ld, n, D, sum.data_ptr(), outer.data_ptr(), _stream())
+    return sum, outer
+
+
+def feature_cov(sum, outer, count):
+    """(mean fp64 [D], cov fp64 [D,D]) = (sum / count, (outer - count mean mean^T) / (count - 1)) from feature_moments' sums."""
+    if not (torch.is_tensor(sum) and sum.dim() == 1 and 1 <= sum.shape[0] <= MAX_FEATURE_DIM):
+        raise ValueError("feature_cov: sum must be fp64 [D], 1 <= D <= %d" % MAX_FEATURE_DIM)
+    D = sum.shape[0]
+    _chk_f64("feature_cov: sum", sum, (D,))
+    _chk_f64("feature_cov: outer", outer, (D, D))
+    if not float(count) >= 2:
+        raise ValueError("feature_cov: count must be at least 2, got %r" % (count,))
+    mean, cov = torch.empty_like(sum), torch.empty_like(outer)
+    call("sg_feature_cov", sum.data_ptr(), outer.data_ptr(), float(count), mean.data_ptr(), cov.data_ptr(), D, _stream())
+    return mean, cov
+
+
+def poly_mmd_sums(x, y, ix=None, iy=None, m=None, gamma=None, coef0=1.0):
+    """Gram sums of the cubic polynomial kernel k(a,b) = (gamma a.b + coef0)^3 over S subsets of m rows each: fp64 [S,3] =
+    {sum_{i!=j} k(X_i,X_j), sum_{i!=j} k(Y_i,Y_j), sum_{i,j} k(X_i,Y_j)} with X_i = x[ix[s,i]], Y_j = y[iy[s,j]].  ix / iy: int32 CUDA
+    [S,m] with every entry a valid row (the caller's contract: fidelity.draw_subsets checks them on the host); both None: ONE subset
+    of the rows 0..m-1 (m defaults to the smaller row count).  gamma defaults to 1 / D."""
+    nx, D, ldx = _chk_rows("poly_mmd_sums: x", x)
+    ny, Dy, ldy = _chk_rows("poly_mmd_sums: y", y)
+    if Dy != D or y.device != x.device:
+        raise ValueError("poly_mmd_sums: x %s and y %s must share D and the device" % (tuple(x.shape), tuple(y.shape)))
+    if (ix is None) != (iy is None):
+        raise ValueError("poly_mmd_sums: give both ix and iy, or neither")
+    if ix is None:
+        S, m = 1, min(nx, ny) if m is None else int(m)
+        if not (1 <= m <= min(nx, ny)):
+            raise ValueError("poly_mmd_sums: m = %d outside [1, %d]" % (m, min(nx, ny)))
+    else:
+        _chk_i32(ix, iy)
+        if ix.dim() != 2 or ix.shape != iy.shape or ix.shape[0] < 1 or ix.shape[1] < 1 or (m is not None and int(m) != ix.shape[1]):
+            raise ValueError("poly_mmd_sums: ix %s / iy %s: expected two [S,m], S, m >= 1" % (tuple(ix.shape), tuple(iy.shape)))
+        S, m = ix.shape
+    nws = lib().sg_poly_mmd_workspace_doubles(S, m)
+    if nws < 1:
+        raise ValueError("poly_mmd_sums: no workspace for S = %d, m = %d" % (S, m))
+    workspace = torch.empty(nws, device=x.device, dtype=torch.float64)
+    sums = torch.empty(S, 3, device=x.device, dtype=torch.float64)
+    call("sg_poly_mmd_sums", x.data_ptr(), ldx, y.data_ptr(), ldy, None if ix is None else ix.data_ptr(), None if iy is None else iy.data_ptr(),
+         S, m, D, float(1.0 / D if gamma is None else gamma), float(coef0), workspace.data_ptr(), sums.data_ptr(), _stream())
+    return sums
+
+
 # ---------------------------------------------------------------- loss head
 def loss_sums(d_r, d_f, s_my, s_f, s_r, r_f, r_r, mode: int):
     _chk(d_r, d_f, s_my, s_f, s_r, r_f, r_r)
