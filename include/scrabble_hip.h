@@ -28,7 +28,8 @@ extern "C" {
 /* flags */
 #define SG_RELU_IN 1   /* max(x,0) applied to the activation operand while it is loaded        */
 #define SG_ACCUM 2     /* out += result                                                          */
-#define SG_RELU_OUT 4  /* max(.,0) applied to the result                                          */
+#define SG_RELU_OUT 4  /* max(.,0) applied to the result; with SG_ACCUM AFTER the accumulate: out = relu(conv + bias + bias2 + out),
+                        * on every route (SG_TANH_OUT likewise) */
 #define SG_TANH_OUT 8  /* tanh applied to the result (Cout == 1 path)                             */
 #define SG_UPS2_IN 64   /* sg_conv2d_bwd_data_wino / sg_conv2d_bwd_weight_wino with tile = 4 only: the gradient operand dy is given at HALF
                          * resolution [B,H/2,W/2,Cout] and stands for 0.25 * upsample2x2(dy) -- the backward of tf.nn.pool(AVG) (resnet_ops.py:105-106)

@@ -1317,7 +1317,9 @@ __global__ __launch_bounds__(512, 2) void sg_wgrad_bf16v2_kernel(const SgWgrad2A
   const unsigned long long p_base64 = (unsigned long long)reinterpret_cast<uintptr_t>(p.p) + 2ull * (unsigned)c0 +
                                       (STRIDED ? 0ull : 2ull * (unsigned long long)m_begin * p.Cp);
   const unsigned long long q_base64 = (unsigned long long)reinterpret_cast<uintptr_t>(p.q) + 2ull * (unsigned)n0 + 2ull * (unsigned long long)m_begin * p.Cq;
-  const int pp_adv = p.p_sy * Ws * adv_y + p.p_sx * adv_x, pp_wrap = Ws * (p.p_sy - 1);      // STRIDED: advance of ppix per tile / per x wrap
+  // STRIDED: advance of ppix per tile / per x wrap.  ppix is linear in the row index b H + y, so 64 pixels are (64 / HW) H whole-sample rows
+  // plus the in-plane advance: with H W == 64 a tile is exactly one sample (adv_y = adv_x = 0) and the cursor moves by Hs Ws
+  const int pp_adv = p.p_sy * Ws * (adv_y + (64 / HW) * p.H) + p.p_sx * adv_x, pp_wrap = Ws * (p.p_sy - 1);
   const unsigned long long z_base64 = (unsigned long long)reinterpret_cast<uintptr_t>(zero);
   const long tap_shift = (long)tdy * p.W + tdx;                      // pixel shift of the tap (may be negative)
   // LDS: P stage 0 | P stage 1 | Q stage 0 | Q stage 1

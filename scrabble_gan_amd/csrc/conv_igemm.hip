@@ -353,6 +353,7 @@ __global__ __launch_bounds__(256) void k_relu_inplace(float* x, long n4) {
 
 static int g_split_override = -1;   // tuning/debug: -1 = heuristic, 1 = never split, n > 1 = force n splits
 extern "C" void sg_debug_set_splitk(int n) { g_split_override = n; }
+int sg_split_override() { return g_split_override; }
 extern "C" void sg_debug_set_splitk_v2(int n);          // conv_bf16v2.hip: the second-generation kernels' own override
 static int g_deterministic = 0;
 bool sg_deterministic() { return g_deterministic != 0; }
@@ -617,6 +618,7 @@ __global__ __launch_bounds__(256) void sg_thin_contract_kernel(const SgThinArgs 
       float v = s + bias;
       if (p.mask && p.mask[m] <= 0.f) v = 0.f;
       if (accum) v += p.out[m];
+      if (p.flags & SG_RELU_OUT) v = fmaxf(v, 0.f);
       if (tanh_out) v = tanhf(v);
       p.out[m] = v;
     }

@@ -317,9 +317,13 @@ static int launch_bf16_cfg(const SgIgemmArgs& a_in, hipStream_t s) {
   const bool can_split = !(a.flags & SG_RELU_OUT) && ((a.flags & SG_ACCUM) || (a.flags & SG_IDENT_OUT));
   constexpr int CUS = 256;
   int full = tiles, nsplit = 1;
-  if (can_split && KT_all >= 16) {        // same balance model as launch_cfg in conv_igemm.hip
+  const int split_ov = sg_split_override();     // 1 (deterministic mode too): never split; n > 1: every tile cut n ways
+  if (can_split && split_ov != 1 && KT_all >= 16) {        // same balance model as launch_cfg in conv_igemm.hip
     const int rem = tiles % CUS;
-    if (rem > 0) {
+    if (split_ov > 1) {
+      full = 0;
+      nsplit = split_ov < KT_all ? split_ov : 1;
+    } else if (rem > 0) {
       const int full_c = tiles < 3 * CUS ? 0 : (tiles - rem) / n_tiles * n_tiles;
       const int tail = tiles - full_c;
       auto cost = [&](int sp) {
@@ -412,6 +416,18 @@ extern "C" int sg_conv2d_transpose_fwd_bf16(const float* x, const void* wp, cons
                                             int H, int W, int Cin, int Cout, int kh, int kw, int sh, int sw, int flags, void* stream) {
   if (!x || !wp || !y || kh * kw > SG_MAX_TAPS || sh < 1 || sw < 1) return SG_ERR_ARG;
   const int pbh = (sh == 1) ? kh / 2 : 0, pbw = (sw == 1) ? kw / 2 : 0;
+  // a parity class without a tap only writes its bias (the fp32 entry point handles it): refuse BEFORE any class is launched, so
+  // that y is untouched when the caller falls back
+  for (int py = 0; py < sh; ++py) {
+    bool any = false;
+    for (int ky = 0; ky < kh; ++ky) any = any || (py + pbh - ky) % sh == 0;
+    if (!any) return SG_ERR_UNSUPPORTED;
+  }
+  for (int px = 0; px < sw; ++px) {
+    bool any = false;
+    for (int kx = 0; kx < kw; ++kx) any = any || (px + pbw - kx) % sw == 0;
+    if (!any) return SG_ERR_UNSUPPORTED;
+  }
   for (int py = 0; py < sh; ++py)
     for (int px = 0; px < sw; ++px) {
       SgIgemmArgs a{};

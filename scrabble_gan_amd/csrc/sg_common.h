@@ -49,6 +49,9 @@ static inline int sg_launch_status() {
 // -- forward / data-grad launches are not cut along the reduction, weight-grad launches run ONE pixel chunk per
 // (tap, c-tile, n-tile), so every dW element has exactly one adder and its summation order is fixed.
 bool sg_deterministic();
+// the reduction-split override of the first-generation launches (sg_debug_set_splitk; sg_set_deterministic writes 1): -1 = the
+// heuristic, 1 = never split, n > 1 = every tile cut n ways
+int sg_split_override();
 
 static inline int sg_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
