@@ -127,8 +127,8 @@ int sg_conv2d_bwd_weight_wino(const float* x, const float* dy, float* dw, float*
                               int B, int H, int W, int Cin, int Cout, int flags, int tile, void* workspace, long workspace_bytes, void* stream);
 
 /* ---- second-generation bf16 path: bf16 ACTIVATIONS in HBM, operand tiles moved global -> LDS by DMA (round 2).
- *      sg_cvt_bf16: fp32 [n] -> bf16 [n] (round to nearest even), n % 8 == 0; relu != 0 applies max(.,0) first; rowscale
- *      (nullable, [n / rowlen], rowlen % 8 == 0) multiplies row r by rowscale[r] first (the per-sample factors of the shared
+ *      sg_cvt_bf16: fp32 [n] -> bf16 [n] (round to nearest even), n % 8 == 0; relu != 0 applies max(.,0) before the rounding; rowscale
+ *      (nullable, [n / rowlen], rowlen % 8 == 0) multiplies row r by rowscale[r] before the ReLU (the per-sample factors of the shared
  *      backward sweep, data_utils.py:449-468 of the reference run as one sweep).
  *      sg_conv2d_fwd_bf16v2 / sg_conv2d_bwd_data_bf16v2: contracts of sg_conv2d_fwd / sg_conv2d_bwd_data
  *      (resnet_ops.py:65,98,103,109) with the activation operand given as a bf16 NHWC tensor (x16 / dy16), the filter as the
@@ -137,6 +137,15 @@ int sg_conv2d_bwd_weight_wino(const float* x, const float* dy, float* dw, float*
  *      tensor is written; not with SG_ACCUM); mask16 (nullable) may replace the fp32 ReLU mask by its bf16 copy.  SG_ERR_UNSUPPORTED unless
  *      reduction channels % 64 == 0 and output channels % 64 == 0:
  *      the caller then uses sg_conv2d_fwd_bf16 / sg_conv2d_bwd_data_bf16 on the fp32 tensor. ----------------------- */
+/* Contract of the operand producers (sg_cvt_bf16, sg_cvt_bf16_bias, sg_pack_filter_bf16 / _fp8, sg_amax_f32, sg_amax2_f32, sg_cvt_fp8,
+ * sg_cvt_fp8_bf16, sg_cvt_fp8_grad, sg_avgpool2_bwd_bf16 / _fp8), enforced bit for bit by tests/test_lowp_producers_gpu.py:
+ *   - Order, one fp32 rounding per step: sg_cvt_bf16 multiplies by the row factor, THEN applies the ReLU, then rounds to nearest even;
+ *     the fp8 producers apply the ReLU (sg_cvt_fp8, sg_cvt_fp8_bf16) or the row factor (e5m2 copies) first, then multiply by the
+ *     scale s = fl(448 / amax) (e5m2: fl(57344 / amax)), then clamp to +-448 (+-57344), then round to nearest even with subnormals
+ *     (the pool kernels multiply by 0.25 before all of that).  For ANY amax > 0, however small, a zero stays a zero and the error
+ *     stays at or below half a step of the format.
+ *   - amax == 0 means scale 1 (an all-zero tensor gives all-zero codes).
+ *   - Inputs must be finite: a NaN or an infinity in the tensor gives unspecified operand bytes (not tested). */
 int sg_cvt_bf16(const float* x, void* out, long n, int relu, const float* rowscale, long rowlen, void* stream);
 /* sg_cvt_bf16 of a [M, C] gradient fused with its bias gradient (resnet_ops.py:65 bias of the conv whose weight-grad
  * follows): out bf16 = rowscale[m / rows_per_sample] * x (rowscale nullable), out_plain (nullable) bf16 = x unscaled (the

@@ -1658,10 +1658,7 @@ extern "C" int sg_amax_f32(const float* x, long n, float* amax, void* stream) {
   return sg_launch_status();
 }
 
-__device__ __forceinline__ float sg8_scale(const float* amax) {
-  const float a = amax[0];
-  return a > 0.f ? 448.f / a : 1.f;
-}
+__device__ __forceinline__ SgFp8Scale sg8_scale(const float* amax) { return sg_fp8_scale(amax[0], 448.f); }
 
 __device__ __forceinline__ unsigned sg8_pack4(float a, float b, float c, float d) {
   int w = 0;
@@ -1671,14 +1668,15 @@ __device__ __forceinline__ unsigned sg8_pack4(float a, float b, float c, float d
 }
 
 __global__ __launch_bounds__(256) void k_cvt_fp8(const float* __restrict__ x, uint2* __restrict__ out, long n8, int relu, const float* amax) {
-  const float s = sg8_scale(amax);
+  const SgFp8Scale s = sg8_scale(amax);
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n8; e += (long)gridDim.x * blockDim.x) {
     float4 v0 = reinterpret_cast<const float4*>(x)[2 * e], v1 = reinterpret_cast<const float4*>(x)[2 * e + 1];
     if (relu) {
       v0.x = fmaxf(v0.x, 0.f); v0.y = fmaxf(v0.y, 0.f); v0.z = fmaxf(v0.z, 0.f); v0.w = fmaxf(v0.w, 0.f);
       v1.x = fmaxf(v1.x, 0.f); v1.y = fmaxf(v1.y, 0.f); v1.z = fmaxf(v1.z, 0.f); v1.w = fmaxf(v1.w, 0.f);
     }
-    out[e] = make_uint2(sg8_pack4(v0.x * s, v0.y * s, v0.z * s, v0.w * s), sg8_pack4(v1.x * s, v1.y * s, v1.z * s, v1.w * s));
+    out[e] = make_uint2(sg8_pack4(sg_fp8_mul(v0.x, s), sg_fp8_mul(v0.y, s), sg_fp8_mul(v0.z, s), sg_fp8_mul(v0.w, s)),
+                         sg8_pack4(sg_fp8_mul(v1.x, s), sg_fp8_mul(v1.y, s), sg_fp8_mul(v1.z, s), sg_fp8_mul(v1.w, s)));
   }
 }
 
@@ -1692,7 +1690,7 @@ extern "C" int sg_cvt_fp8(const float* x, void* out, long n, int relu, const flo
 
 // the same conversion from a bf16 tensor (an operand-only conv result): out = e4m3(relu?(float(x16)) * 448 / amax[0]); n % 8 == 0
 __global__ __launch_bounds__(256) void k_cvt_fp8_bf16(const bf16x8* __restrict__ x, uint2* __restrict__ out, long n8, int relu, const float* amax) {
-  const float s = sg8_scale(amax);
+  const SgFp8Scale s = sg8_scale(amax);
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n8; e += (long)gridDim.x * blockDim.x) {
     const bf16x8 h = x[e];
     float v[8];
@@ -1700,7 +1698,7 @@ __global__ __launch_bounds__(256) void k_cvt_fp8_bf16(const bf16x8* __restrict__
     for (int j = 0; j < 8; ++j) {
       v[j] = (float)h[j];
       if (relu) v[j] = fmaxf(v[j], 0.f);
-      v[j] *= s;
+      v[j] = sg_fp8_mul(v[j], s);
     }
     out[e] = make_uint2(sg8_pack4(v[0], v[1], v[2], v[3]), sg8_pack4(v[4], v[5], v[6], v[7]));
   }
@@ -1716,7 +1714,7 @@ extern "C" int sg_cvt_fp8_bf16(const void* x16, void* out, long n, int relu, con
 // filter packing: fp32 [taps][K][N] (transpose = 1) or [taps][N][K] (transpose = 0) -> fp8 [taps][N][K], scaled by 448 / amax
 __global__ __launch_bounds__(256) void k_pack_filter_fp8(const float* w, unsigned char* out, const float* amax, int K, int N, int transpose) {
   __shared__ float tile[32][33];
-  const float s = sg8_scale(amax);
+  const SgFp8Scale s = sg8_scale(amax);
   const int t = blockIdx.z;
   const float* wt = w + (size_t)t * K * N;
   unsigned char* ot = out + (size_t)t * K * N;
@@ -1736,7 +1734,7 @@ __global__ __launch_bounds__(256) void k_pack_filter_fp8(const float* w, unsigne
 #pragma unroll
   for (int r = ty; r < 32; r += 8) {
     const int n = n0 + r, k = k0 + tx;
-    if (n < N && k < K) ot[(size_t)n * K + k] = (unsigned char)(sg8_pack4(tile[tx][r] * s, 0.f, 0.f, 0.f) & 0xffu);
+    if (n < N && k < K) ot[(size_t)n * K + k] = (unsigned char)(sg8_pack4(sg_fp8_mul(tile[tx][r], s), 0.f, 0.f, 0.f) & 0xffu);
   }
 }
 

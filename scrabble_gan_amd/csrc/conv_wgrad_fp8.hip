@@ -343,8 +343,7 @@ __global__ __launch_bounds__(256) void k_cvt_fp8_grad(const float* __restrict__ 
                                                       const float* __restrict__ amax2, float* __restrict__ dbias, int rows_per_block) {
   __shared__ float red[256 * 8];
   const float a_plain = amax2[0], a_scaled = amax2[1];
-  const float s4 = a_plain > 0.f ? 448.f / a_plain : 1.f;
-  const float s5 = a_scaled > 0.f ? 57344.f / a_scaled : 1.f;
+  const SgFp8Scale s4 = sg_fp8_scale(a_plain, 448.f), s5 = sg_fp8_scale(a_scaled, 57344.f);
   const int c8 = C >> 3;
   int CL = 256;
   while (CL > c8) CL >>= 1;
@@ -360,14 +359,14 @@ __global__ __launch_bounds__(256) void k_cvt_fp8_grad(const float* __restrict__ 
         const float4* src = reinterpret_cast<const float4*>(x + m * C + 8 * cg);
         float4 v0 = src[0], v1 = src[1];
         if (out_e4m3)
-          out_e4m3[(m * C + 8 * cg) >> 3] = make_uint2(sg8w_pack4_e4m3(v0.x * s4, v0.y * s4, v0.z * s4, v0.w * s4),
-                                                       sg8w_pack4_e4m3(v1.x * s4, v1.y * s4, v1.z * s4, v1.w * s4));
+          out_e4m3[(m * C + 8 * cg) >> 3] = make_uint2(sg8w_pack4_e4m3(sg_fp8_mul(v0.x, s4), sg_fp8_mul(v0.y, s4), sg_fp8_mul(v0.z, s4), sg_fp8_mul(v0.w, s4)),
+                                                       sg8w_pack4_e4m3(sg_fp8_mul(v1.x, s4), sg_fp8_mul(v1.y, s4), sg_fp8_mul(v1.z, s4), sg_fp8_mul(v1.w, s4)));
         if (rowscale) {
           const float f = rowscale[m / rows_per_sample];
           v0.x *= f; v0.y *= f; v0.z *= f; v0.w *= f; v1.x *= f; v1.y *= f; v1.z *= f; v1.w *= f;
         }
-        out_e5m2[(m * C + 8 * cg) >> 3] = make_uint2(sg8w_pack4_e5m2(v0.x * s5, v0.y * s5, v0.z * s5, v0.w * s5),
-                                                     sg8w_pack4_e5m2(v1.x * s5, v1.y * s5, v1.z * s5, v1.w * s5));
+        out_e5m2[(m * C + 8 * cg) >> 3] = make_uint2(sg8w_pack4_e5m2(sg_fp8_mul(v0.x, s5), sg_fp8_mul(v0.y, s5), sg_fp8_mul(v0.z, s5), sg_fp8_mul(v0.w, s5)),
+                                                     sg8w_pack4_e5m2(sg_fp8_mul(v1.x, s5), sg_fp8_mul(v1.y, s5), sg_fp8_mul(v1.z, s5), sg_fp8_mul(v1.w, s5)));
         s[0] += v0.x; s[1] += v0.y; s[2] += v0.z; s[3] += v0.w; s[4] += v1.x; s[5] += v1.y; s[6] += v1.z; s[7] += v1.w;
       }
     }

@@ -34,11 +34,11 @@ __global__ __launch_bounds__(256) void k_avgpool2_bwd_lowp(const float* __restri
                                                            float* __restrict__ amax_out, int B, int H, int W, int C) {
   const int c8n = C >> 3, Ho = H >> 1, Wo = W >> 1;
   const long total = (long)B * H * W * c8n;
-  float s4 = 1.f, s5 = 1.f;
+  SgFp8Scale s4{1.f, 1.f}, s5{1.f, 1.f};
   if constexpr (FP8) {
     const float a0 = 0.25f * amax_in[0], a1 = 0.25f * amax_in[1];
-    s4 = a0 > 0.f ? 448.f / a0 : 1.f;
-    s5 = a1 > 0.f ? 57344.f / a1 : 1.f;
+    s4 = sg_fp8_scale(a0, 448.f);
+    s5 = sg_fp8_scale(a1, 57344.f);
     if (blockIdx.x == 0 && threadIdx.x == 0) { amax_out[0] = a0; amax_out[1] = a1; }
   }
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
@@ -52,8 +52,8 @@ __global__ __launch_bounds__(256) void k_avgpool2_bwd_lowp(const float* __restri
     v0.x *= 0.25f; v0.y *= 0.25f; v0.z *= 0.25f; v0.w *= 0.25f; v1.x *= 0.25f; v1.y *= 0.25f; v1.z *= 0.25f; v1.w *= 0.25f;
     if (out_a) {
       if constexpr (FP8) {
-        reinterpret_cast<uint2*>(out_a)[e] = make_uint2(lp_pack4_e4m3(v0.x * s4, v0.y * s4, v0.z * s4, v0.w * s4),
-                                                        lp_pack4_e4m3(v1.x * s4, v1.y * s4, v1.z * s4, v1.w * s4));
+        reinterpret_cast<uint2*>(out_a)[e] = make_uint2(lp_pack4_e4m3(sg_fp8_mul(v0.x, s4), sg_fp8_mul(v0.y, s4), sg_fp8_mul(v0.z, s4), sg_fp8_mul(v0.w, s4)),
+                                                        lp_pack4_e4m3(sg_fp8_mul(v1.x, s4), sg_fp8_mul(v1.y, s4), sg_fp8_mul(v1.z, s4), sg_fp8_mul(v1.w, s4)));
       } else {
         bf16x8 h;
         h[0] = (__bf16)v0.x; h[1] = (__bf16)v0.y; h[2] = (__bf16)v0.z; h[3] = (__bf16)v0.w;
@@ -67,8 +67,8 @@ __global__ __launch_bounds__(256) void k_avgpool2_bwd_lowp(const float* __restri
         v0.x *= f; v0.y *= f; v0.z *= f; v0.w *= f; v1.x *= f; v1.y *= f; v1.z *= f; v1.w *= f;
       }
       if constexpr (FP8) {
-        reinterpret_cast<uint2*>(out_b)[e] = make_uint2(lp_pack4_e5m2(v0.x * s5, v0.y * s5, v0.z * s5, v0.w * s5),
-                                                        lp_pack4_e5m2(v1.x * s5, v1.y * s5, v1.z * s5, v1.w * s5));
+        reinterpret_cast<uint2*>(out_b)[e] = make_uint2(lp_pack4_e5m2(sg_fp8_mul(v0.x, s5), sg_fp8_mul(v0.y, s5), sg_fp8_mul(v0.z, s5), sg_fp8_mul(v0.w, s5)),
+                                                        lp_pack4_e5m2(sg_fp8_mul(v1.x, s5), sg_fp8_mul(v1.y, s5), sg_fp8_mul(v1.z, s5), sg_fp8_mul(v1.w, s5)));
       } else {
         bf16x8 h;
         h[0] = (__bf16)v0.x; h[1] = (__bf16)v0.y; h[2] = (__bf16)v0.z; h[3] = (__bf16)v0.w;

@@ -93,6 +93,22 @@ __device__ __forceinline__ void sg_atomic_max_nonneg(float* amax, float m) {
   atomicMax(p, bits);
 }
 
+// Per-tensor fp8 scale top / amax (top = 448 for e4m3, 57344 for e5m2; 1 when amax == 0), kept as a pair: the scaled value is
+// (x * pre) * mul.  pre = 1 and mul = fl(top / amax) -- bit for bit x * fl(top / amax) -- unless that quotient overflows fp32 (a normal
+// amax below top / FLT_MAX: 1.3e-36 / 1.7e-34).  An infinite scale would send every non-zero element to the clamp end and every zero to
+// 0 * inf = NaN, which fminf / fmaxf turn into -top; there pre = 2^64 (exact: |x| <= amax is far from overflow) and
+// mul = top / (amax * 2^64), finite for every amax down to the smallest subnormal.
+struct SgFp8Scale {
+  float pre, mul;
+};
+__device__ __forceinline__ SgFp8Scale sg_fp8_scale(float amax, float top) {
+  if (!(amax > 0.f)) return SgFp8Scale{1.f, 1.f};
+  const float s = top / amax;
+  if (s <= 3.402823466e38f) return SgFp8Scale{1.f, s};
+  return SgFp8Scale{0x1p64f, top / (amax * 0x1p64f)};
+}
+__device__ __forceinline__ float sg_fp8_mul(float x, SgFp8Scale s) { return (x * s.pre) * s.mul; }
+
 __device__ __forceinline__ double sg_wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
