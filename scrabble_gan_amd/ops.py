@@ -10,6 +10,7 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import operands as _operands
 from ._lib import call, lib
 
 RELU_IN, ACCUM, RELU_OUT, TANH_OUT = 1, 2, 4, 8
@@ -258,7 +259,15 @@ class net_stream:
                 t.record_stream(self.main)
 
 
-_GHOSTS = set()        # storage pointers of the never-written fp32 handles behind operand-only results (bf16 / fp8 modes), this step
+# Which bf16 / fp8 copy of an fp32 tensor a kernel reads, the never-written ("ghost") fp32 handles behind operand-only results, the fp8
+# amax slots and the kept Winograd transforms of this step: all bookkeeping lives in operands.py, this module launches.
+_OPERANDS = _operands.Registry()
+_GHOST_PTRS = _OPERANDS.ghosts          # (the registry's own set: _p() runs once per pointer argument of every launch)
+
+
+def _ghost_error(t: torch.Tensor) -> RuntimeError:
+    return RuntimeError("fp32 contents of an operand-only result requested (shape %s): its consumers must read the bf16 / fp8 copy; "
+                        "conv dtype / deterministic mode changed between the forward and the backward pass?" % (tuple(t.shape),))
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -268,9 +277,8 @@ def _p(t: Optional[torch.Tensor]):
     instead of computing on uninitialised memory."""
     if t is None:
         return None
-    if _GHOSTS and t.untyped_storage().data_ptr() in _GHOSTS:
-        raise RuntimeError("fp32 contents of an operand-only result requested (shape %s): its consumers must read the bf16 / fp8 copy; "
-                           "conv dtype / deterministic mode changed between the forward and the backward pass?" % (tuple(t.shape),))
+    if _GHOST_PTRS and t.untyped_storage().data_ptr() in _GHOST_PTRS:
+        raise _ghost_error(t)
     return t.data_ptr()
 
 
@@ -309,8 +317,7 @@ def set_conv_dtype(dtype: str) -> None:
         raise ValueError("conv dtype must be 'f32', 'bf16' or 'fp8'")
     CONV_DTYPE = dtype
     _PACK_CACHE.clear()
-    _TWINS.clear()
-    _GHOSTS.clear()
+    _OPERANDS.clear()
 
 
 _FP8_BLOCK = [0]
@@ -337,14 +344,16 @@ def _fp8_ok(K: int, N: int, kh: int, kw: int, same: bool) -> bool:
 
 def fp8_of(t: torch.Tensor, relu: bool = False):
     """-> (fp8 e4m3 copy of relu?(t) * 448 / amax as a uint8 tensor, amax device scalar); one conversion per (t, relu)."""
-    key = (t.untyped_storage().data_ptr(), "fp8", bool(relu), t.storage_offset(), t.numel())
-    e = _TWINS.get(key)
+    e = _OPERANDS.get_fp8(t, relu)
     if e is None:
         _chk(t)
         out = torch.empty(t.shape, device=t.device, dtype=torch.uint8)
         if _is_ghost(t):                         # an operand-only conv result: quantise its bf16 values, scale = the recorded
             t16 = _twin_get(t)                   # amax of the whole tensor (a batch slice shares it)
-            amax = _TWINS[(t.untyped_storage().data_ptr(), "amax")][1][0:1]
+            pair = _OPERANDS.storage_amax(t)
+            if t16 is None or pair is None:      # (a pooled-gradient ghost: it carries no bf16 values / no amax to quantise them with)
+                raise _ghost_error(t)
+            amax = pair[0:1]
             with _hbm("cvt_fp8", t16, out):
                 call("sg_cvt_fp8_bf16", t16.data_ptr(), out.data_ptr(), t.numel(), int(relu), _p(amax), _stream())
         else:
@@ -354,9 +363,8 @@ def fp8_of(t: torch.Tensor, relu: bool = False):
                 if rec is None:
                     call("sg_amax_f32", _p(t), t.numel(), _p(amax), _stream())
                 call("sg_cvt_fp8", _p(t), out.data_ptr(), t.numel(), int(relu), _p(amax), _stream())
-        e = (t, out, amax)
-        _TWINS[key] = e
-    return e[1], e[2]
+        e = _OPERANDS.put_fp8(t, relu, out, amax)
+    return e.data, e.amax
 
 
 def _fp8_wgrad_ok(Cin: int, Cout: int, kh: int, kw: int, same: bool) -> bool:
@@ -369,15 +377,13 @@ def grad_operand_fp8(dy: torch.Tensor, sample_scale, want_colsum: bool):
     """The fp8 weight-grad operand of a gradient tensor: (e5m2 copy of sample_scale[b] * dy[b] as uint8, its amax device scalar,
     fp32 column sums or None).  ONE amax sweep (max |dy| and max |scale dy| together) and ONE convert sweep yield that copy, the
     column sums (= the bias gradient) and -- when the gradient has none yet -- the e4m3 copy the data-grad launch of the same
-    gradient reads (registered under fp8_of's key); kept for the step."""
-    key = (dy.untyped_storage().data_ptr(), "g8", 0 if sample_scale is None else sample_scale.data_ptr(), dy.storage_offset(), dy.numel())
-    e = _TWINS.get(key)
-    if e is None or (want_colsum and e[4] is None):
+    gradient reads (registered as the copy fp8_of finds); kept for the step."""
+    e = _OPERANDS.get_grad_fp8(dy, sample_scale)
+    if e is None or (want_colsum and e.colsum is None):
         _chk(dy, sample_scale)
         C = dy.shape[-1]
         M = dy.numel() // C
-        k4 = (dy.untyped_storage().data_ptr(), "fp8", False, dy.storage_offset(), dy.numel())
-        have4 = k4 in _TWINS
+        have4 = _OPERANDS.get_fp8(dy, False) is not None
         rec = _amax_get(dy, sample_scale, need_scaled=True)
         amax2 = rec if rec is not None else torch.zeros(2, device=dy.device)
         out5 = torch.empty(dy.shape, device=dy.device, dtype=torch.uint8)
@@ -390,41 +396,35 @@ def grad_operand_fp8(dy: torch.Tensor, sample_scale, want_colsum: bool):
             call("sg_cvt_fp8_grad", _p(dy), out5.data_ptr(), None if out4 is None else out4.data_ptr(), M, C, _p(sample_scale), rows,
                  _p(amax2), _p(colsum), _stream())
         if out4 is not None:
-            _TWINS[k4] = (dy, out4, amax2[0:1])
-        e = (dy, sample_scale, out5, amax2[1:2], colsum, amax2)
-        _TWINS[key] = e
-    return e[2], e[3], e[4]
+            _OPERANDS.put_fp8(dy, False, out4, amax2[0:1])
+        e = _OPERANDS.put_grad_fp8(dy, sample_scale, out5, amax2[1:2], colsum, amax2)
+    return e.data, e.amax, e.colsum
 
 
 def _amax2_of(dy: torch.Tensor, sample_scale) -> torch.Tensor:
     """Device pair {max |dy|, max |sample_scale dy|}: from the gradient's fp8 operand entry when it has one, else one read sweep."""
-    sptr = 0 if sample_scale is None else sample_scale.data_ptr()
-    e = _TWINS.get((dy.untyped_storage().data_ptr(), "g8", sptr, dy.storage_offset(), dy.numel()))
+    e = _OPERANDS.get_grad_fp8(dy, sample_scale)
     if e is not None:
-        return e[5]
+        return e.amax2
     rec = _amax_get(dy, sample_scale, need_scaled=True)
     if rec is not None:
         return rec
-    key = (dy.untyped_storage().data_ptr(), "a2", sptr, dy.storage_offset(), dy.numel())
-    e = _TWINS.get(key)
-    if e is None:
+    amax2 = _OPERANDS.get_amax2(dy, sample_scale)
+    if amax2 is None:
         _chk(dy, sample_scale)
         amax2 = torch.zeros(2, device=dy.device)
         rows = (dy.numel() // sample_scale.numel()) if sample_scale is not None else 4
         with _hbm("cvt_fp8", dy):
             call("sg_amax2_f32", _p(dy), dy.numel(), _p(sample_scale), rows, _p(amax2), _stream())
-        e = (dy, amax2)
-        _TWINS[key] = e
-    return e[1]
+        _OPERANDS.put_amax2(dy, sample_scale, amax2)
+    return amax2
 
 
 def _grad_colsum(dy: torch.Tensor, sample_scale) -> torch.Tensor:
     """fp32 column sums of sample_scale[b] * dy[b] (a bias gradient), from whichever operand entry of the gradient holds them."""
-    sptr = 0 if sample_scale is None else sample_scale.data_ptr()
-    base = (dy.untyped_storage().data_ptr(), dy.storage_offset(), dy.numel())
-    e = _TWINS.get((base[0], "g8", sptr, base[1], base[2]))
-    if e is not None and e[4] is not None:
-        return e[4]
+    e = _OPERANDS.get_grad_fp8(dy, sample_scale)
+    if e is not None and e.colsum is not None:
+        return e.colsum
     return grad_operand(dy, sample_scale, True)[1]
 
 
@@ -433,8 +433,7 @@ OPERAND_ONLY_MIN_TILES = 512     # conv1 -> conv2 chains keep the intermediate a
                                  # tiles (smaller launches want the reduction-split tail, which meets in the fp32 result)
 
 
-def _is_ghost(t: torch.Tensor) -> bool:
-    return (t.untyped_storage().data_ptr(), "ghost") in _TWINS
+_is_ghost = _OPERANDS.is_ghost
 
 
 def operand_only_ok(B: int, H: int, W: int, C: int) -> bool:
@@ -466,9 +465,7 @@ def avgpool2_bwd_operands(dout: torch.Tensor, wscale=None, want_dw: bool = True)
     ghost = torch.empty(B, H, W, C, device=dout.device, dtype=torch.float32)
     if GHOST_NAN:
         ghost.fill_(float("nan"))
-    gp, n = ghost.untyped_storage().data_ptr(), ghost.numel()
-    _GHOSTS.add(gp)
-    sptr = 0 if wscale is None else wscale.data_ptr()
+    _OPERANDS.mark_ghost(ghost)
     colsum = _grad_colsum(dout, wscale) if want_dw else None
     if use16:
         plain = torch.empty(ghost.shape, device=dout.device, dtype=torch.bfloat16)
@@ -477,7 +474,7 @@ def avgpool2_bwd_operands(dout: torch.Tensor, wscale=None, want_dw: bool = True)
             call("sg_avgpool2_bwd_bf16", _p(dout), plain.data_ptr(), None if scaled is None else scaled.data_ptr(), _p(wscale), B, H, W, C, _stream())
         _twin_put(ghost, plain)
         if want_dw:
-            _TWINS[(gp, sptr, 0, n)] = (ghost, wscale, plain if scaled is None else scaled, colsum)
+            _OPERANDS.put_grad_bf16(ghost, wscale, plain if scaled is None else scaled, colsum)
     else:
         a2 = _amax2_of(dout, wscale)
         out4 = torch.empty(ghost.shape, device=dout.device, dtype=torch.uint8)
@@ -486,11 +483,10 @@ def avgpool2_bwd_operands(dout: torch.Tensor, wscale=None, want_dw: bool = True)
         with _hbm("pool", dout, out4, out5):
             call("sg_avgpool2_bwd_fp8", _p(dout), out4.data_ptr(), None if out5 is None else out5.data_ptr(), _p(wscale), _p(a2), _p(amax_dx),
                  B, H, W, C, _stream())
-        _TWINS[(gp, "fp8", False, 0, n)] = (ghost, out4, amax_dx[0:1])
+        _OPERANDS.put_fp8(ghost, False, out4, amax_dx[0:1])
         if want_dw:
-            _TWINS[(gp, "g8", sptr, 0, n)] = (ghost, wscale, out5, amax_dx[1:2], colsum, amax_dx)
+            _OPERANDS.put_grad_fp8(ghost, wscale, out5, amax_dx[1:2], colsum, amax_dx)
     return ghost
-
 
 
 def packed_filter_fp8(w: torch.Tensor, kind: str):
@@ -577,26 +573,14 @@ def _bf16_ok(K: int, N: int) -> bool:
 # ---- bf16 twins (second-generation bf16 path, conv_bf16v2.hip) ---------------------------------------------------
 # In bf16 mode the large convolutions read their activation operand as a bf16 NHWC tensor.  A "twin" is the bf16 copy of
 # an fp32 activation: written by the producing conv's epilogue (y16 / dx16) or by sg_cvt_bf16 on first use, and found
-# again through this registry (keyed by the fp32 tensor's storage; a batch slice of a registered tensor maps to the
-# same slice of its twin).  An entry holds a reference to the fp32 tensor, so its storage cannot be recycled while the
-# entry lives; kernels that write INTO an existing tensor drop its entry (_touch).  new_step() empties the registry.
+# again through the operand registry (operands.py: keyed by the fp32 tensor's storage; a batch slice of a registered
+# tensor maps to the same slice of its twin).  Kernels that write INTO an existing tensor drop its record (_touch);
+# new_step() empties the registry.
 USE_V2 = _os.environ.get("SG_BF16_V2", "1") == "1"
-_TWINS = {}
-
-
-_AMAX_POOL = {}        # raw stream handle -> {"buf", "next"}: a pool is zeroed and handed out on ONE stream (its slots are written by that
-                       # stream's conv epilogues and read by that stream's conversion kernels, or behind a join)
 
 
 def _amax_slot(like: torch.Tensor) -> torch.Tensor:
-    """Two zeroed floats (max |t|, max |scale t|) from a per-step, per-stream pool: ONE memset launch per 1024 convolutions."""
-    pool = _AMAX_POOL.setdefault(_stream(), {"buf": None, "next": 0})
-    if pool["buf"] is None or pool["next"] + 2 > pool["buf"].numel() or pool["buf"].device != like.device:
-        pool["buf"] = torch.zeros(2048, device=like.device)
-        pool["next"] = 0
-    s = pool["buf"][pool["next"]:pool["next"] + 2]
-    pool["next"] += 2
-    return s
+    return _OPERANDS.amax_slot(_stream(), like.device)
 
 
 def _want_amax() -> bool:
@@ -604,71 +588,46 @@ def _want_amax() -> bool:
     return CONV_DTYPE == "fp8" and not _FP8_BLOCK[0]
 
 
-def _amax_put(t: torch.Tensor, slot: torch.Tensor, scale) -> None:
-    if t.storage_offset() == 0 and t.numel() * 4 == t.untyped_storage().nbytes():
-        _TWINS[(t.untyped_storage().data_ptr(), "amax")] = (t, slot, 0 if scale is None else scale.data_ptr())
+_amax_put = _OPERANDS.put_amax      # (t, slot, scale): whole tensors only
+_amax_get = _OPERANDS.get_amax      # (t, scale=None, need_scaled=False) -> the producer-recorded amax pair of a WHOLE tensor, or None
 
 
-def _amax_get(t: torch.Tensor, scale=None, need_scaled: bool = False):
-    """The producer-recorded amax pair of a WHOLE tensor, or None.  need_scaled: element 1 must belong to `scale`."""
-    e = _TWINS.get((t.untyped_storage().data_ptr(), "amax"))
-    if e is None or t.storage_offset() != 0 or t.numel() != e[0].numel():
-        return None
-    if need_scaled and e[2] != (0 if scale is None else scale.data_ptr()):
-        return None
-    return e[1]
+def _result_copies(out: torch.Tensor, want16, amax: bool):
+    """Before a second-generation conv launch: -> (bf16 copy its epilogue writes beside `out` or None, amax slot or None)."""
+    t16 = torch.empty(out.shape, device=out.device, dtype=torch.bfloat16) if want16 else None
+    return t16, (_amax_slot(out) if amax else None)
+
+
+def _result_register(out: torch.Tensor, t16, am, scale) -> None:
+    """After that launch: what the epilogue wrote beside `out` is found through `out` for the rest of the step."""
+    if am is not None:
+        _amax_put(out, am, scale)
+    if t16 is not None:
+        _twin_put(out, t16)
 
 
 def new_step() -> None:
-    _TWINS.clear()
-    _GHOSTS.clear()
-    _AMAX_POOL.clear()
-    _WINO_V["map"].clear()
-    _WINO_V["on"] = WINO_KEEP_V
+    _OPERANDS.new_step(WINO_KEEP_V)
 
 
 def end_step() -> None:
     """The step's backward sweeps are queued: the kept Winograd transforms are released (and launches outside a step keep none)."""
-    _WINO_V["map"].clear()
-    _WINO_V["on"] = False
+    _OPERANDS.end_step()
 
 
-def _touch(t) -> None:
-    if t is not None and _WINO_V["map"]:
-        _WINO_V["map"].pop(t.untyped_storage().data_ptr(), None)
-    if t is not None and _TWINS:
-        k = t.untyped_storage().data_ptr()
-        _GHOSTS.discard(k)
-        _TWINS.pop(k, None)
-        for kk in [kk for kk in _TWINS if isinstance(kk, tuple) and kk[0] == k]:
-            del _TWINS[kk]
+_touch = _OPERANDS.touch      # before a kernel writes into an existing tensor (None: nothing to do)
 
 
 def bf16_scaled(t: torch.Tensor, rowscale: torch.Tensor) -> torch.Tensor:
     """bf16 copy of rowscale[b] * t[b] (the weight-grad operand of a shared backward sweep); one conversion per (t, rowscale)."""
-    key = (t.untyped_storage().data_ptr(), rowscale.data_ptr(), t.storage_offset(), t.numel())
-    e = _TWINS.get(key)
+    e = _OPERANDS.get_grad_bf16(t, rowscale)
     if e is None:
-        e = (t, rowscale, cvt_bf16(t, rowscale=rowscale), None)
-        _TWINS[key] = e
-    return e[2]
+        e = _OPERANDS.put_grad_bf16(t, rowscale, cvt_bf16(t, rowscale=rowscale), None)
+    return e.data
 
 
-def _twin_put(t: torch.Tensor, t16: torch.Tensor) -> None:
-    if t.storage_offset() != 0 or t.numel() * 4 != t.untyped_storage().nbytes():
-        return
-    if len(_TWINS) > 512:
-        _TWINS.clear()
-        _GHOSTS.clear()
-    _TWINS[t.untyped_storage().data_ptr()] = (t, t16.view(-1))
-
-
-def _twin_get(t: torch.Tensor):
-    e = _TWINS.get(t.untyped_storage().data_ptr())
-    if e is None:
-        return None
-    off = t.storage_offset()
-    return e[1][off:off + t.numel()].view(t.shape)
+_twin_put = _OPERANDS.put_bf16      # (t, t16): whole tensors only
+_twin_get = _OPERANDS.get_bf16      # (t) -> the bf16 twin of t (of a batch slice: that slice of the twin), or None
 
 
 def cvt_bf16(t: torch.Tensor, relu=False, rowscale=None) -> torch.Tensor:
@@ -701,24 +660,21 @@ def grad_operand(dy: torch.Tensor, sample_scale, want_colsum: bool):
     None).  Whatever is missing -- the scaled copy, the column sums (= the bias gradient of every conv that produced dy's
     forward tensor: conv2 and the 1x1 shortcut of a ResNetBlockDown share them) and, when the gradient has no plain twin yet,
     that twin too (the data-grad launch of the same gradient wants it) -- is made in ONE sweep over dy and kept for the step."""
-    key = (dy.untyped_storage().data_ptr(), 0 if sample_scale is None else sample_scale.data_ptr(), dy.storage_offset(), dy.numel())
-    e = _TWINS.get(key)
+    e = _OPERANDS.get_grad_bf16(dy, sample_scale)
     plain = _twin_get(dy)
-    if e is None or (want_colsum and e[3] is None):
-        whole = dy.storage_offset() == 0 and dy.numel() * 4 == dy.untyped_storage().nbytes()
+    if e is None or (want_colsum and e.colsum is None):
         colsum = torch.zeros(dy.shape[-1], device=dy.device, dtype=torch.float32)
         if sample_scale is None:
             t16 = cvt_bf16_bias(dy, None, colsum)
             if plain is None:
                 _twin_put(dy, t16)
-        elif plain is None and whole:
+        elif plain is None and _operands.whole(dy):
             t16, p16 = cvt_bf16_bias(dy, sample_scale, colsum, want_plain=True)
             _twin_put(dy, p16)
         else:
             t16 = cvt_bf16_bias(dy, sample_scale, colsum)
-        e = (dy, sample_scale, t16, colsum)
-        _TWINS[key] = e
-    return e[2], e[3]
+        e = _OPERANDS.put_grad_bf16(dy, sample_scale, t16, colsum)
+    return e.data, e.colsum
 
 
 def bf16_of(t: torch.Tensor) -> torch.Tensor:
@@ -765,22 +721,17 @@ _WINO_WS = {}              # raw stream handle -> scratch buffer (V and Mt of th
 # finds it again through the input's storage -- a batch slice of the input maps to a row range of every plane -- instead of
 # transforming relu(x) a second time.
 WINO_KEEP_V = _os.environ.get("SG_WINO_KEEP_V", "1") == "1"
-_WINO_V = {"on": False, "map": {}}      # map: storage pointer of x -> (x, relu_in, tile, V [P * Tp * K], Tp)
 
 
 def _wino_v_get(x: torch.Tensor, relu_in: bool, tile: int):
     """-> (pointer of the first row of x's tiles in plane 0, rows between planes) or None"""
-    e = _WINO_V["map"].get(x.untyped_storage().data_ptr())
-    if e is None or e[1] != relu_in or e[2] != tile or e[0].shape[1:] != x.shape[1:]:
+    hit = _OPERANDS.kept(x, relu_in, tile)
+    if hit is None:
         return None
-    per = x.shape[1] * x.shape[2] * x.shape[3]
-    off = x.storage_offset() - e[0].storage_offset()
-    if off < 0 or off % per or off // per + x.shape[0] > e[0].shape[0]:
-        return None
-    t0 = (off // per) * (x.shape[1] // tile) * (x.shape[2] // tile)
-    if e[5] != _stream():                   # read on another stream than the one it was made on (weight-grads on the sweep's side stream)
-        e[3].record_stream(torch.cuda.current_stream())
-    return e[3].data_ptr() + 4 * t0 * x.shape[3], e[4]
+    e, t0 = hit
+    if e.stream != _stream():               # read on another stream than the one it was made on (weight-grads on the sweep's side stream)
+        e.V.record_stream(torch.cuda.current_stream())
+    return e.V.data_ptr() + 4 * t0 * x.shape[3], e.plane_rows
 
 
 def _wino_tile(H: int, W: int) -> int:
@@ -847,13 +798,11 @@ def _wino_conv(a, w, out, bias, bias2, mask, K: int, N: int, relu_in: bool, flag
     Tp = -(-T // 128) * 128                 # = sg_wino_plane_rows(B, H, W, tile)
     nbytes = 4 * P * Tp * (K + N)           # = sg_wino_workspace_bytes(B, H, W, K, N, tile)
     s = _stream()
-    keep = (fwd and _WINO_V["on"] and a.storage_offset() == 0 and _wino_wgrad_ok(K, N, 3, 3, True, H, W)
+    keep = (fwd and _OPERANDS.keeping and a.storage_offset() == 0 and _wino_wgrad_ok(K, N, 3, 3, True, H, W)
             and (tile == 2 or T >= WINO4_WGRAD_MIN_TILES))
     if keep:                                # V in a tensor of its own (the weight gradient reads it again), Mt in the stream's scratch
         Vt = torch.empty(P * Tp * K, device=a.device, dtype=torch.float32)
-        if len(_WINO_V["map"]) > 256:
-            _WINO_V["map"].clear()
-        _WINO_V["map"][a.untyped_storage().data_ptr()] = (a, bool(relu_in), tile, Vt, Tp, s)
+        _OPERANDS.keep(a, relu_in, tile, Vt, Tp, s)
         V = Vt.data_ptr()
         Mt = _wino_workspace(4 * P * Tp * N, a).data_ptr()
         if PROFILER is None:
@@ -1009,8 +958,7 @@ def conv2d_fwd(x, w, bias=None, bias2=None, same=True, relu_in=False, relu_out=F
     if only:
         if GHOST_NAN:
             out.fill_(float("nan"))
-        _TWINS[(out.untyped_storage().data_ptr(), "ghost")] = (out,)
-        _GHOSTS.add(out.untyped_storage().data_ptr())
+        _OPERANDS.mark_ghost(out)
     if _wino_ok(Cin, Cout, kh, kw, same, H, W, B) and not tanh_out:
         _wino_conv(x, w, out, bias, bias2, None, Cin, Cout, relu_in, _flags(False, accum, relu_out),
                    ("wino_fwd", B, Ho, Wo, Cin, Cout, kh))
@@ -1020,23 +968,16 @@ def conv2d_fwd(x, w, bias=None, bias2=None, same=True, relu_in=False, relu_out=F
         if use8:
             x8, ax = fp8_of(x, relu_in)                       # the operand ReLU is folded into the conversion
             w8, aw = packed_filter_fp8(w, "fwd")
-            y16 = torch.empty(out.shape, device=out.device, dtype=torch.bfloat16) if want16 else None
-            am = _amax_slot(out)
+            y16, am = _result_copies(out, want16, True)
             call("sg_conv2d_fwd_fp8", x8.data_ptr(), _p(ax), w8.data_ptr(), _p(aw), _p(bias), _p(bias2), None if only else _p(out),
                  None if y16 is None else y16.data_ptr(), B, H, W, Cin, Cout, kh, kw, int(same), _flags(False, accum, relu_out), _p(am), _stream())
-            _amax_put(out, am, None)
-            if y16 is not None:
-                _twin_put(out, y16)
+            _result_register(out, y16, am, None)
         elif _v2_ok(Cin, Cout, kh, kw, same) and not tanh_out:
             x16 = bf16_of(x)
-            y16 = torch.empty(out.shape, device=out.device, dtype=torch.bfloat16) if want16 else None
-            am = _amax_slot(out) if _want_amax() else None
+            y16, am = _result_copies(out, want16, _want_amax())
             call("sg_conv2d_fwd_bf16v2", x16.data_ptr(), packed_filter(w, "fwd").data_ptr(), _p(bias), _p(bias2), None if only else _p(out),
                  None if y16 is None else y16.data_ptr(), B, H, W, Cin, Cout, kh, kw, int(same), _flags(relu_in, accum, relu_out), _p(am), _stream())
-            if am is not None:
-                _amax_put(out, am, None)
-            if y16 is not None:
-                _twin_put(out, y16)
+            _result_register(out, y16, am, None)
         elif _f32v2_ok(Cin, Cout, kh, kw, same, out.shape[0] * out.shape[1] * out.shape[2]) and not tanh_out:
             call("sg_conv2d_fwd_v2", _p(x), _p(packed_filter(w, "fwd_f32t")), _p(bias), _p(bias2), _p(out), B, H, W, Cin, Cout, kh, kw,
                  int(same), _flags(relu_in, accum, relu_out), _stream())
@@ -1070,28 +1011,21 @@ def conv2d_bwd_data(dy, w, in_hw: Tuple[int, int], mask=None, same=True, out=Non
         if use8:
             dy8, ady = fp8_of(dy)
             w8, aw = packed_filter_fp8(w, "bwd")
-            dx16 = torch.empty(out.shape, device=out.device, dtype=torch.bfloat16) if want16 else None
+            dx16, am = _result_copies(out, want16, True)
             m16 = None if mask is None else _twin_get(mask)
-            am = _amax_slot(out)
             call("sg_conv2d_bwd_data_fp8", dy8.data_ptr(), _p(ady), w8.data_ptr(), _p(aw), None if m16 is not None else _p(mask),
                  None if m16 is None else m16.data_ptr(), _p(out), None if dx16 is None else dx16.data_ptr(), B, H, W, Cin, Cout,
                  kh, kw, int(same), _flags(accum=accum), _p(am), _p(amax_scale), _stream())
-            _amax_put(out, am, amax_scale)
-            if dx16 is not None:
-                _twin_put(out, dx16)
+            _result_register(out, dx16, am, amax_scale)
         elif _v2_ok(Cout, Cin, kh, kw, same):
             dy16 = bf16_of(dy)
-            dx16 = torch.empty(out.shape, device=out.device, dtype=torch.bfloat16) if want16 else None
+            dx16, am = _result_copies(out, want16, _want_amax())
             m16 = None if mask is None else _twin_get(mask)          # the ReLU mask as bf16 when a twin exists (half the bytes)
-            am = _amax_slot(out) if _want_amax() else None
             call("sg_conv2d_bwd_data_bf16v2", dy16.data_ptr(), packed_filter(w, "bwd").data_ptr(), None if m16 is not None else _p(mask),
                  None if m16 is None else m16.data_ptr(), _p(out),
                  None if dx16 is None else dx16.data_ptr(), B, H, W, Cin, Cout, kh, kw, int(same), _flags(accum=accum), _p(am),
                  _p(amax_scale), _stream())
-            if am is not None:
-                _amax_put(out, am, amax_scale)
-            if dx16 is not None:
-                _twin_put(out, dx16)
+            _result_register(out, dx16, am, amax_scale)
         elif _f32v2_ok(Cout, Cin, kh, kw, same, B * H * W):
             call("sg_conv2d_bwd_data_v2", _p(dy), _p(w), _p(mask), _p(out), B, H, W, Cin, Cout, kh, kw, int(same), _flags(accum=accum), _stream())
         elif _bf16_ok(Cout, Cin):

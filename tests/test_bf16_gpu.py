@@ -247,9 +247,9 @@ def test_grad_operand_bundle_shared_by_conv2_and_shortcut(dev, bf16_mode):
     dw2, db2 = torch.zeros(3, 3, Cout, Cout, device=dev), torch.zeros(Cout, device=dev)
     dws, dbs = torch.zeros(1, 1, Cin, Cout, device=dev), torch.full((Cout,), 2.0, device=dev)
     ops.conv2d_bwd_weight(c1, dy, dw2, relu_in=True, db=db2, sample_scale=sc)
-    n_entries = len(ops._TWINS)
+    n_entries = ops._OPERANDS.count()
     ops.conv2d_bwd_weight(x, dy, dws, db=dbs, sample_scale=sc)
-    assert len(ops._TWINS) == n_entries + 1                     # only x's twin is new: dy's bundle was reused
+    assert ops._OPERANDS.count() == n_entries + 1               # only x's twin is new: dy's bundle was reused
     ref = (dy.double() * sc.double().view(B, 1, 1, 1)).sum(dim=(0, 1, 2))
     assert (db2.double() - ref).abs().max().item() <= 1e-5 * ref.abs().max().item()
     assert (dbs.double() - 2.0 - ref).abs().max().item() <= 1e-5 * ref.abs().max().item()

@@ -798,6 +798,9 @@ def test_wrappers(dev):
             fp = factors(Bp)
             dd, fd = _dev32(dev, d), _dev32(dev, fp)
             gh = ops.avgpool2_bwd_operands(dd, fd, True)
+            assert ops._is_ghost(gh), "the pooled-gradient handle carries no ghost mark (%s mode)" % mode
+            with pytest.raises(RuntimeError):       # no fp32 contents, and no e4m3 copy of relu(d_c2) was asked of the producer
+                ops.fp8_of(gh, relu=True)
             if mode == "bf16":
                 want_p, want_s = L.avgpool2_bwd_bf16(d, fp)
                 same_bits(_host(ops.bf16_of(gh), np.uint16), want_p, "ops.avgpool2_bwd_operands bf16 plain", None, 0x8000)

@@ -238,14 +238,14 @@ def test_weight_grad_reuses_the_forward_transform(dev, wino_everywhere, B, H, W,
     ops.new_step()
     try:
         y = ops.conv2d_fwd(x, w, relu_in=True)
-        assert ops._WINO_V["map"], "the forward launch kept nothing"
+        assert ops._OPERANDS.kept_count(), "the forward launch kept nothing"
         kept = ops._wino_v_get(x[2:], True, ops._wino_tile(H, W))
         assert kept is not None and kept[1] == -(-(B * (H // ops._wino_tile(H, W)) * (W // ops._wino_tile(H, W))) // 128) * 128
         got = [grads(0, B), grads(2, B), grads(0, 2)]
         assert ops._wino_v_get(x, False, ops._wino_tile(H, W)) is None            # (another operand ReLU: not the same transform)
     finally:
         ops.end_step()
-    assert not ops._WINO_V["map"] and not ops._WINO_V["on"]
+    assert not ops._OPERANDS.kept_count() and not ops._OPERANDS.keeping
     for (dw, db), (rw, rb), name in zip(got, ref, ("whole batch", "samples 2..", "samples ..2")):
         _close(dw, rw, 1e-5, "dW with the kept transform, " + name)
         _close(db, rb, 1e-5, "db, " + name)
