@@ -12,6 +12,9 @@ tensor drops that tensor's record (`touch`, O(1)), `clear()` drops all of them.
   pair answers only for the whole tensor (`storage_amax` is the one reader that lets a slice share it).
 * The fp8 copy and the two gradient bundles are made per request and are specific to (offset, numel) -- the fp8 copy
   also to `relu`, the bundles and the stand-alone amax pair to the pointer of their per-sample scale (0: no scale).
+  Every entry keyed by a scale holds a reference to the scale tensor, so its address names it for as long as the entry
+  lives.  The CONTENTS are not part of the key: a per-sample scale tensor must not be rewritten within a step, because the
+  copies made with its old factors are keyed by its address and would be found again.
 * A ghost mark (one set of storage pointers, `ghosts`): the fp32 tensor is a never-written handle; its consumers must
   read the copies.
 
@@ -36,6 +39,7 @@ AMAX_POOL_FLOATS = 2048
 class Amax:
     pair: torch.Tensor                  # {max |t|, max |scale t|}, written by the producing conv's epilogue
     scale_ptr: int                      # the scale element 1 belongs to (0: none)
+    scale: Optional[torch.Tensor] = None    # (kept alive: a freed scale's address could be handed to another [B] tensor)
 
 
 @dataclass(slots=True)
@@ -69,6 +73,7 @@ class Record:
     grad_bf16: Dict[tuple, GradBf16] = field(default_factory=dict)      # (scale_ptr, offset, numel) ->
     grad_fp8: Dict[tuple, GradFp8] = field(default_factory=dict)        # (scale_ptr, offset, numel) ->
     amax2: Dict[tuple, torch.Tensor] = field(default_factory=dict)      # (scale_ptr, offset, numel) -> stand-alone amax pair
+    amax2_scale: Dict[tuple, torch.Tensor] = field(default_factory=dict)    # (the scales of those keys, kept alive; not counted)
 
     def count(self) -> int:
         return (self.bf16 is not None) + (self.amax is not None) + len(self.fp8) + len(self.grad_bf16) + len(self.grad_fp8) + len(self.amax2)
@@ -126,6 +131,11 @@ class Registry:
         self._records.clear()
         self.ghosts.clear()
 
+    def drop_copies(self) -> None:
+        """Every copy goes (the conv dtype changed mid-step); the ghost marks stay, each with an empty record that keeps its storage
+        alive: a never-written handle remains one, so its consumers fail loudly instead of reading it as fp32."""
+        self._records = {k: Record(r.owner) for k, r in self._records.items() if k in self.ghosts}
+
     def new_step(self, keep_transforms: bool) -> None:
         self.clear()
         self._amax_pool.clear()
@@ -161,7 +171,7 @@ class Registry:
 
     def put_amax(self, t: torch.Tensor, pair: torch.Tensor, scale) -> None:
         if whole(t):
-            self.record(t).amax = Amax(pair, 0 if scale is None else scale.data_ptr())
+            self.record(t).amax = Amax(pair, 0 if scale is None else scale.data_ptr(), scale)
 
     def get_amax(self, t: torch.Tensor, scale=None, need_scaled: bool = False) -> Optional[torch.Tensor]:
         """The producer-recorded amax pair of a WHOLE tensor, or None.  need_scaled: element 1 must belong to `scale`."""
@@ -207,7 +217,10 @@ class Registry:
         return None if r is None else r.amax2.get(_by_scale(t, scale))
 
     def put_amax2(self, t: torch.Tensor, scale, pair: torch.Tensor) -> torch.Tensor:
-        self.record(t).amax2[_by_scale(t, scale)] = pair
+        r, k = self.record(t), _by_scale(t, scale)
+        r.amax2[k] = pair
+        if scale is not None:
+            r.amax2_scale[k] = scale
         return pair
 
     # ---- amax slots

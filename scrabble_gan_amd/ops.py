@@ -317,7 +317,7 @@ def set_conv_dtype(dtype: str) -> None:
         raise ValueError("conv dtype must be 'f32', 'bf16' or 'fp8'")
     CONV_DTYPE = dtype
     _PACK_CACHE.clear()
-    _OPERANDS.clear()
+    _OPERANDS.drop_copies()         # (ghost marks outlive the change: see _p)
 
 
 _FP8_BLOCK = [0]
@@ -1266,6 +1266,7 @@ def resample_u8(src_u8: torch.Tensor, desc, mode: int, out_kind: int, out: Optio
     if out is not None and not (out.is_cuda and out.is_contiguous() and out.dtype == want):
         raise ValueError("out must be a contiguous %s CUDA tensor" % want)
     d, need = check_resample_desc(desc, src_u8.numel(), None if out is None else out.numel(), out_kind)
+    _touch(out)
     device = src_u8.device if src_u8.is_cuda else (out.device if out is not None else torch.device("cuda", torch.cuda.current_device()))
     if not src_u8.is_cuda:
         src_u8 = src_u8.to(device, non_blocking=True)
@@ -1730,7 +1731,8 @@ def rmsprop_update(p, g, ms, lr, rho=0.9, eps=1e-7):
 # ---------------------------------------------------------------- averaged generator (averaging.py)
 def ema_update(ema, p, one_minus_decay: float):
     """ema += one_minus_decay * (p - ema) in place over two flat buffers.  `one_minus_decay` is 1 - decay as the caller computed
-    it in double; it is rounded to fp32 once, here.  0 leaves `ema` bitwise unchanged, 1 makes it bitwise `p`."""
+    it in double; it is rounded to fp32 once, here.  0 leaves `ema` bitwise unchanged, 1 makes it bitwise `p`.  `ema` is rewritten
+    through a raw pointer: a caller whose target holds a model's weights calls weights_changed()."""
     _chk(ema, p)
     if ema.numel() != p.numel():
         raise ValueError("ema_update: %d vs %d elements" % (ema.numel(), p.numel()))
@@ -1856,10 +1858,14 @@ def mul_mask(x, mask, rows_per_mask=1):
 
 
 def lstm_cell_fwd(z, z_off, ldz, c_prev, c_out, h_out, h_off, ldh, h_copy, hc_off, ldc, B, H):
+    """Rewrites z in place and writes c_out, h_out and h_copy through raw pointers without dropping operand copies: these tensors
+    feed GEMMs only and must not carry bf16 / fp8 copies."""
     call("sg_lstm_cell_fwd", z.data_ptr() + 4 * z_off, ldz, _p(c_prev), _p(c_out), h_out.data_ptr() + 4 * h_off, ldh,
          None if h_copy is None else h_copy.data_ptr() + 4 * hc_off, ldc, B, H, _stream())
 
 
 def lstm_cell_bwd(gates, g_off, ldz, c_prev, c_t, dh_a, a_off, lda, dh_b, dc_next, dc_prev, B, H):
+    """Writes its gradients (in place over the gate block, and dc_prev) through raw pointers without dropping operand copies: these
+    tensors feed GEMMs only and must not carry bf16 / fp8 copies."""
     call("sg_lstm_cell_bwd", gates.data_ptr() + 4 * g_off, ldz, _p(c_prev), _p(c_t), dh_a.data_ptr() + 4 * a_off, lda, _p(dh_b),
          _p(dc_next), _p(dc_prev), B, H, _stream())

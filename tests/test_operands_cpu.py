@@ -189,3 +189,68 @@ def test_the_cap_empties_everything(reg):
     reg.put_bf16(last, last.to(torch.bfloat16))                         # one record over the cap: all the others go, ghost marks included
     assert reg.count() == 1 and not reg.ghosts and reg.get_bf16(last) is not None
     assert not any(reg.is_ghost(t) for t in owners) and all(reg.get_bf16(t) is None for t in owners)
+
+
+class _AtAddress:
+    """Stands in for a [B] scale tensor that the allocator placed at a given address."""
+
+    def __init__(self, ptr):
+        self.ptr = ptr
+
+    def data_ptr(self):
+        return self.ptr
+
+
+def test_amax_entry_keeps_its_scale_alive(reg):
+    """The amax pair is matched by the ADDRESS of its scale, so the entry must own the scale: once freed, its address could be handed
+    to another [B] tensor with other factors, and element 1 of the pair would answer for them."""
+    import gc
+    import weakref
+    x, pair = f32(4, 2, 3, 8), torch.zeros(2)
+    s1 = torch.ones(4)
+    old, alive = s1.data_ptr(), weakref.ref(s1)
+    before = reg.count()
+    reg.put_amax(x, pair, s1)
+    assert reg.count() == before + 1                                    # (the kept scale is no copy of its own)
+    del s1
+    gc.collect()
+    assert alive() is not None and alive().data_ptr() == old, "the amax entry let go of its scale: its address can be recycled"
+    assert reg.find(x).amax.scale is alive()
+    later = [torch.full((4,), 8.0) for _ in range(64)]                  # same size: what the allocator would hand the freed block to
+    assert all(t.data_ptr() != old for t in later)
+    assert reg.get_amax(x, _AtAddress(old), need_scaled=True) is pair   # whoever is at that address IS the kept scale ...
+    assert torch.equal(alive(), torch.ones(4))                          # ... and still holds the factors the pair was taken with
+    assert reg.get_amax(x, later[0], need_scaled=True) is None
+    reg.touch(x)                                                        # the record goes, and the scale with it
+    gc.collect()
+    assert alive() is None and reg.get_amax(x, _AtAddress(old), need_scaled=True) is None
+    s2 = torch.ones(4)                                                  # the stand-alone pair is keyed the same way and keeps its scale too
+    alive2 = weakref.ref(s2)
+    reg.put_amax2(x, s2, pair)
+    assert reg.count() == 1
+    del s2
+    gc.collect()
+    assert alive2() is not None and reg.get_amax2(x, alive2()) is pair
+    reg.touch(x)
+    gc.collect()
+    assert alive2() is None
+
+
+def test_amax_without_a_scale_keeps_nothing(reg):
+    x, pair = f32(4, 2, 3, 8), torch.zeros(2)
+    reg.put_amax(x, pair, None)
+    a = reg.find(x).amax
+    assert a.scale is None and a.scale_ptr == 0 and reg.count() == 1
+    assert reg.get_amax(x, None, need_scaled=True) is pair and reg.get_amax(x, _AtAddress(0), need_scaled=True) is pair
+
+
+def test_drop_copies_keeps_the_ghost_marks(reg):
+    x, y, s = f32(2, 2, 4, 8), f32(2, 2, 4, 8), torch.ones(2)
+    _fill(reg, x, s)                                                    # a ghost with every kind of copy
+    reg.put_bf16(y, y.to(torch.bfloat16))
+    reg.put_fp8(y, False, u8(y), torch.zeros(1))
+    reg.drop_copies()
+    assert reg.count() == 1 and reg.is_ghost(x) and reg.find(x).count() == 0 and reg.find(x).owner is x
+    assert reg.find(y) is None and reg.get_bf16(x) is None and reg.storage_amax(x) is None
+    reg.touch(x)
+    assert reg.count() == 0 and not reg.ghosts
