@@ -321,6 +321,28 @@ int sg_edit_distance(const int* hyp, const int* hyp_len, int hyp_stride, const i
                      int* dist, int B, void* stream);
 /* sums fp64 [4] += {sum dist, sum ref_len, #(dist != 0), B}: additive over batches and ranks, the caller zeroes it once */
 int sg_legibility_sums(const int* dist, const int* ref_len, int B, double* sums, void* stream);
+/* CTC prefix beam search (csrc/ctc_beam.hip) on the lp [B,T,C] of sg_ctc_log_probs, frames t < input_length, optionally
+ * rescored by a dense character n-gram LM.  A beam entry is a prefix l (labels in [0, C-2]) with pb / pnb, the log-mass of its
+ * alignments that end in blank / non-blank, and acc, its LM and length credit; the search starts from {(): pb 0, pnb -inf,
+ * acc 0}.  Per frame every entry l of the previous beam, tot = lse(pb, pnb),
+ *   stays:   pb'(l) (+)= tot + lp[t,blank];  pnb'(l) (+)= pnb + lp[t,last(l)] (nothing for the empty prefix)
+ *   extends by every c < C-1:  pnb'(l+c) (+)= lp[t,c] + (pb if c == last(l) else tot);
+ *            acc(l+c) = acc(l) + len_bonus + lm_weight * lm[ctx(l), c]   (no LM term when lm is null)
+ * (+) is log-add-exp over all contributions to the same STRING (a prefix that left the beam and is re-created still merges
+ * into its surviving extension).  The new beam: the `beam` strings of highest lse(pb', pnb') + acc; a tie goes to the lower
+ * (slot of the parent) * C + c, a stay counting as c = C-1.  After the last frame a survivor scores
+ * lse(pb, pnb) + acc + lm_weight * lm[ctx(l), C-1]; survivors are returned best first.
+ * lm (nullable): fp32 [C^(lm_order-1), C] log-probabilities, lm_order in {1,2,3}; ctx = the last lm_order-1 labels, oldest
+ * first, base C, with the digit C-1 at a missing position (start of word); column c < C-1 = next character c, column C-1 = end
+ * of word.  out_labels int32 [B,nbest,out_stride] (-1 behind each string), out_len int32 [B,nbest], out_score fp32 [B,nbest];
+ * nbest slots past the number of survivors: length 0, score -inf.  No float atomics: two calls on one input agree bitwise.
+ * SG_ERR_ARG before any launch: a null required pointer, B < 1, C outside [2,64], beam outside [1,64], nbest outside [1,beam],
+ * input_length outside [1,T], out_stride < input_length, lm_order outside [1,3] with an lm.  SG_ERR_UNSUPPORTED:
+ * input_length > 256.  workspace: sg_ctc_beam_workspace_bytes bytes (-1 on bad sizes; 0 today: the search lives in LDS). */
+long sg_ctc_beam_workspace_bytes(int B, int input_length, int beam);
+int sg_ctc_beam_decode(const float* lp, int B, int T, int C, int input_length, int beam, const float* lm, int lm_order,
+                       float lm_weight, float len_bonus, int* out_labels, int* out_len, float* out_score, int nbest,
+                       int out_stride, void* workspace, void* stream);
 
 /* ---- losses + gradient balancing + statistics (net_loss.py:4-54; data_utils.py:418-442,476-490) */
 /* mode 0 hinge, 1 not_saturating.  sums: fp64 [12] (all-reduce across ranks between the two calls) */

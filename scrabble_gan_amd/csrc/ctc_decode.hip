@@ -7,18 +7,7 @@
 //   k_legibility_sums   fp64 {sum dist, sum ref_len, #(dist != 0), B}
 // Blank = last class.  Wave-shaped like ctc.hip: lanes are classes (C <= 64), frames (64 per chunk), extended-label states
 // (2 len + 1 <= 64) or reference positions (ref_len <= 63); neighbours come from __shfl, flags from __ballot.
-#include "sg_common.h"
-
-__device__ __forceinline__ float dec_lse2(float a, float b) {
-  const float m = fmaxf(a, b);
-  if (m == -INFINITY) return -INFINITY;
-  return m + logf(expf(a - m) + expf(b - m));
-}
-__device__ __forceinline__ float dec_lse3(float a, float b, float c) {
-  const float m = fmaxf(a, fmaxf(b, c));
-  if (m == -INFINITY) return -INFINITY;
-  return m + logf(expf(a - m) + expf(b - m) + expf(c - m));
-}
+#include "ctc_common.h"      // dec_lse2 / dec_lse3
 
 // One frame, lanes = classes; `a` is the lane's logit (-inf for lane >= C).  The same operations in the same order as phase A
 // of k_softmax_ctc, so a score computed from this lp equals the training loss of the same word.

@@ -2,6 +2,7 @@
 
     python -m scrabble_gan_amd.evaluate --recognizer-weights run/checkpoints/recognizer/15/cktp-15 [--my-rec] \
         (--data DIR | --synthetic) [--batches 20] [--batch-size 64] [--lexicon words.txt] \
+        [--beam 16 [--lm-corpus words.txt | --lm lm.npz] [--lm-order 2] [--lm-weight 0.5] [--len-bonus 0.0]] \
         [--generator-weights run/checkpoints/generator/15/cktp-15 --words machine learning]
         [--fidelity 10000 [--feature-space recognizer|discriminator] [--discriminator-weights PREFIX] [--real-stats real.npz]
          [--kid-subsets 100] [--kid-subset-size 1000]]
@@ -10,8 +11,13 @@
 `--data DIR` is the bucket-folder layout the train loop reads (<DIR>/<L>/<name>.png + .txt); `--synthetic` takes the
 uniform-noise batches of `main.py --synthetic` (no dataset at hand: the rates then only show that the path runs).
 With `--lexicon FILE` (one word per line) every image is also read as the lexicon word of lowest CTC cost.  With
-`--generator-weights` each of `--words` is rendered in inference mode and read back.  Prints ONE JSON line:
-{cer, wer, n_words, n_chars[, cer_lexicon, wer_lexicon][, read_back: [{target, read, distance}], cer_fake, wer_fake]
+`--generator-weights` each of `--words` is rendered in inference mode and read back.  With `--beam W` (W > 0) every image is
+also read by a CTC prefix beam search W strings wide (open vocabulary), optionally rescored by a character n-gram LM counted
+from `--lm-corpus FILE` (one word per line, order `--lm-order`; words with characters outside `--char-vec` are skipped and
+counted on stderr) or loaded from `--lm FILE.npz` (legibility.CharLM.save); `--lm-weight` scales the LM's log-probabilities and
+`--len-bonus` is added per character.  Prints ONE JSON line:
+{cer, wer, n_words, n_chars[, cer_lexicon, wer_lexicon][, cer_beam, wer_beam]
+ [, read_back: [{target, read, distance[, read_beam, distance_beam, score_beam]}], cer_fake, wer_fake[, cer_fake_beam, wer_fake_beam]]
  [, frechet, kid, kid_std, n_real, n_fake, feature_space, dim]}.
 
 `--fidelity N` (with `--generator-weights`) renders N words -- drawn from `--lexicon`, else from the labels of the real batches --
@@ -29,6 +35,50 @@ import json
 import numpy as np
 
 CHAR_VEC = 'abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ'
+
+
+def add_beam_arguments(ap):
+    """The prefix-beam-search flags, shared with run_inference --read-back."""
+    ap.add_argument("--beam", type=int, default=0, metavar="W", help="also read by a CTC prefix beam search W strings wide (0: off)")
+    ap.add_argument("--lm-corpus", default=None, metavar="FILE", help="one word per line: count a character n-gram LM for the beam read")
+    ap.add_argument("--lm", default=None, metavar="FILE.npz", help="a saved character n-gram LM (legibility.CharLM.save)")
+    ap.add_argument("--lm-order", type=int, default=2, choices=[1, 2, 3], help="order of the LM counted from --lm-corpus")
+    ap.add_argument("--lm-weight", type=float, default=0.0, help="weight of the LM's log-probabilities in the beam score")
+    ap.add_argument("--len-bonus", type=float, default=0.0, help="added to the beam score per character")
+
+
+def check_beam_arguments(ap, args):
+    if not (0 <= args.beam <= 64):
+        ap.error("--beam must lie in [0, 64]")
+    if args.lm_corpus and args.lm:
+        ap.error("--lm-corpus and --lm exclude each other")
+    if (args.lm_corpus or args.lm) and not args.beam:
+        ap.error("--lm-corpus / --lm need --beam W")
+
+
+def load_lm(args, char_vec, device):
+    """The CharLM the flags name, on `device`, or None."""
+    import sys
+    from .legibility import CharLM
+    if args.lm:
+        lm = CharLM.load(args.lm)
+        if lm.char_vector != char_vec:
+            raise ValueError("%s was counted over another character vector" % args.lm)
+        return lm.to(device)
+    if args.lm_corpus:
+        with open(args.lm_corpus) as f:
+            words = [w for w in (line.strip() for line in f) if w]
+        lm = CharLM.from_words(words, char_vec, args.lm_order)
+        print("%s: %d words, %d skipped (characters outside the character vector)" % (args.lm_corpus, len(words), lm.skipped), file=sys.stderr)
+        return lm.to(device)
+    return None
+
+
+def beam_keywords(args, char_vec, device) -> dict:
+    """Keyword arguments of legibility.evaluate_recognizer / read_back for the flags; empty at --beam 0."""
+    if not args.beam:
+        return {}
+    return {"beam": args.beam, "lm": load_lm(args, char_vec, device), "lm_weight": args.lm_weight, "len_bonus": args.len_bonus}
 
 
 def parse_args(argv=None):
@@ -54,7 +104,9 @@ def parse_args(argv=None):
     ap.add_argument("--kid-subset-size", type=int, default=1000)
     ap.add_argument("--features-real", default=None, metavar="A.npy", help="precomputed real features [N,D]: no networks needed")
     ap.add_argument("--features-fake", default=None, metavar="B.npy")
+    add_beam_arguments(ap)
     args = ap.parse_args(argv)
+    check_beam_arguments(ap, args)
     if (args.features_real is None) != (args.features_fake is None):
         ap.error("--features-real and --features-fake go together")
     if args.kid_subsets < 1 or args.kid_subset_size < 2:
@@ -114,15 +166,19 @@ def main(argv=None):
         dataset = load_prepare_data(in_dim, args.batch_size, args.data.rstrip("/") + "/", args.char_vec, args.bucket_size)
     lexicon = read_lexicon(args.lexicon, args.char_vec) if args.lexicon else None
     batches = list(itertools.islice(dataset, args.batches))
-    out = legibility.evaluate_recognizer(R, batches, args.char_vec, lexicon)
+    search = beam_keywords(args, args.char_vec, R.device)
+    out = legibility.evaluate_recognizer(R, batches, args.char_vec, lexicon, **search)
     if args.generator_weights:
         G = NA.make_generator(128, in_dim, (32, 8192), None, "B3", n_classes, vis_model=False)
         G.load_weights(args.generator_weights)
         style = np.random.default_rng(0).uniform(-1, 1, (max(1, min(len(args.words), 16)),) + in_dim).astype(np.float32)
-        rb = legibility.read_back(G, R, style, args.words, args.char_vec)
+        rb = legibility.read_back(G, R, style, args.words, args.char_vec, **search)
         out["read_back"] = rb
         out["cer_fake"] = sum(r["distance"] for r in rb) / max(1, sum(len(r["target"]) for r in rb))
         out["wer_fake"] = sum(r["distance"] != 0 for r in rb) / len(rb)
+        if search:
+            out["cer_fake_beam"] = sum(r["distance_beam"] for r in rb) / max(1, sum(len(r["target"]) for r in rb))
+            out["wer_fake_beam"] = sum(r["distance_beam"] != 0 for r in rb) / len(rb)
     if args.fidelity:
         out.update(_fidelity(args, NA, G, R, batches, lexicon, in_dim))
     print(json.dumps(out))

@@ -557,6 +557,15 @@ class RecognizerModel(_Model):
         logits = self.logits(x)
         return ops.ctc_greedy_decode(logits, self._ctc_frames(logits.shape[1]) if input_length is None else input_length)
 
+    def transcribe_beam(self, x, beam=16, lm=None, lm_weight=0.0, len_bonus=0.0, nbest=1, input_length=None):
+        """CTC prefix beam search over the same frames `transcribe` reads, optionally rescored by a character n-gram LM (`lm`: a
+        legibility.CharLM on this device, or None) -> (labels int32 [B,nbest,input_length] with -1 behind each string, lengths
+        int32 [B,nbest], scores fp32 [B,nbest]), best first (ops.ctc_beam_decode)."""
+        logits = self.logits(x)
+        table, order = (None, 1) if lm is None else (lm.table, lm.order)
+        return ops.ctc_beam_decode(ops.ctc_log_probs(logits), self._ctc_frames(logits.shape[1]) if input_length is None else input_length,
+                                   beam=beam, lm=table, lm_order=order, lm_weight=lm_weight, len_bonus=len_bonus, nbest=nbest)
+
     def score_words(self, x, words, word_len, input_length=None):
         """CTC negative log-likelihood [B,W] of every candidate word (int32 [W,stride] rows, int32 [W] lengths) on every
         image: the cost __call__ returns, for W words of mixed lengths from one forward pass."""

@@ -1610,6 +1610,47 @@ def legibility_sums(dist, ref_len, sums=None):
     return sums
 
 
+MAX_BEAM = 64            # csrc/ctc_beam.hip: beam entries, and the longest input_length it takes
+MAX_BEAM_FRAMES = 256
+
+
+def ctc_beam_decode(lp, input_length=None, beam=16, lm=None, lm_order=1, lm_weight=0.0, len_bonus=0.0, nbest=1):
+    """CTC prefix beam search over the frames t < input_length of lp [B,T,C] (ctc_log_probs), `beam` strings wide, optionally
+    rescored by a dense character n-gram LM (fp32 [C**(lm_order-1), C] log-probabilities, column C-1 = end of word; the
+    contract is in include/scrabble_hip.h) -> (labels int32 [B,nbest,input_length] with -1 behind each string,
+    lengths int32 [B,nbest], scores fp32 [B,nbest]), best first; slots past the survivors have length 0 and score -inf."""
+    _chk(lp)
+    if lp.dim() != 3:
+        raise ValueError("lp %s: expected [B,T,C]" % (tuple(lp.shape),))
+    B, T, C = lp.shape
+    input_length = T if input_length is None else int(input_length)
+    beam, nbest, lm_order = int(beam), int(nbest), int(lm_order)
+    if not (2 <= C <= 64):
+        raise ValueError("CTC beam search takes 2 to 64 classes, got %d" % C)
+    if not (0 < input_length <= T):
+        raise ValueError("CTC input_length %d out of range (T = %d)" % (input_length, T))
+    if input_length > MAX_BEAM_FRAMES:
+        raise ValueError("CTC beam search takes at most %d frames, got %d" % (MAX_BEAM_FRAMES, input_length))
+    if not (1 <= beam <= MAX_BEAM) or not (1 <= nbest <= beam):
+        raise ValueError("beam %d must lie in [1, %d] and nbest %d in [1, beam]" % (beam, MAX_BEAM, nbest))
+    if lm is not None:
+        if lm_order not in (1, 2, 3):
+            raise ValueError("lm_order %d: 1, 2 or 3" % lm_order)
+        if not (torch.is_tensor(lm) and lm.is_cuda and lm.is_contiguous() and lm.dtype == torch.float32 and lm.device == lp.device
+                and tuple(lm.shape) == (C ** (lm_order - 1), C)):
+            raise ValueError("lm must be a contiguous fp32 tensor of shape %s on %s" % ((C ** (lm_order - 1), C), lp.device))
+    nws = lib().sg_ctc_beam_workspace_bytes(B, input_length, beam)
+    if nws < 0:
+        raise ValueError("ctc_beam_decode: no workspace size for B %d, input_length %d, beam %d" % (B, input_length, beam))
+    workspace = torch.empty(nws, device=lp.device, dtype=torch.uint8) if nws else None       # (0 today: the search lives in LDS)
+    labels = empty(B, nbest, input_length, like=lp, dtype=torch.int32)
+    lengths = empty(B, nbest, like=lp, dtype=torch.int32)
+    scores = empty(B, nbest, like=lp)
+    call("sg_ctc_beam_decode", _p(lp), B, T, C, input_length, beam, _p(lm), lm_order, float(lm_weight), float(len_bonus),
+         labels.data_ptr(), lengths.data_ptr(), scores.data_ptr(), nbest, input_length, None if workspace is None else workspace.data_ptr(), _stream())
+    return labels, lengths, scores
+
+
 # ---------------------------------------------------------------- fidelity statistics (csrc/fidelity.hip)
 MAX_FEATURE_DIM = 4096
 

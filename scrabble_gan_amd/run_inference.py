@@ -3,13 +3,15 @@
 `generator([style_imgs, labels], training=False)`).
 
     python -m scrabble_gan_amd.run_inference --weights run/checkpoints/generator/15/cktp-15 --words machinelearning \
-        [--style-dir DIR | --synthetic-style] [--count 10] --out words.png [--read-back --recognizer-weights PREFIX [--my-rec]]
+        [--style-dir DIR | --synthetic-style] [--count 10] --out words.png [--read-back --recognizer-weights PREFIX [--my-rec]
+        [--beam 16 [--lm-corpus words.txt | --lm lm.npz] [--lm-order 2] [--lm-weight 0.5] [--len-bonus 0.0]]]
 
 The checkpoint is the `<prefix>.safetensors` file `train()` writes per epoch (`_Model.save_weights`).  BatchNorm runs in
 inference mode (moving statistics).  The output PNG stacks the `count` renderings of each word vertically (the
 reference shows them as a 10 x 1 matplotlib grid) after the reference's (x + 1) / 2 mapping to [0, 1].
 `--read-back` (not in the reference) also has a trained recognizer read each word's first rendering and prints one line per
-word: target, what R read, edit distance (legibility.read_back)."""
+word: target, what R read, edit distance (legibility.read_back); with `--beam W` (W > 0; flags as in evaluate.py) the line goes on
+with the prefix beam search's read, its edit distance and its score."""
 from __future__ import annotations
 
 import argparse
@@ -51,7 +53,8 @@ def save_grid(imgs: np.ndarray, path: str) -> None:
     Image.fromarray(np.concatenate(stack[:-1], axis=0), mode="L").save(path)
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    from .evaluate import add_beam_arguments, check_beam_arguments
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--weights", required=True, help="checkpoint prefix (without .safetensors)")
     ap.add_argument("--words", nargs="+", default=["machinelearning"])
@@ -63,9 +66,26 @@ def main(argv=None):
     ap.add_argument("--read-back", action="store_true", help="print what the recognizer reads from each generated word")
     ap.add_argument("--recognizer-weights", default=None, help="recognizer checkpoint prefix (with --read-back)")
     ap.add_argument("--my-rec", action="store_true", help="the recognizer checkpoint is the BiLSTM model's")
+    add_beam_arguments(ap)
     args = ap.parse_args(argv)
     if args.read_back and not args.recognizer_weights:
         ap.error("--read-back needs --recognizer-weights PREFIX")
+    check_beam_arguments(ap, args)
+    if args.beam and not args.read_back:
+        ap.error("--beam needs --read-back")
+    return args
+
+
+def format_read_back(row: dict) -> str:
+    """One printed line per word; the beam fields only where read_back produced them."""
+    line = "%s\t%s\t%d" % (row["target"], row["read"], row["distance"])
+    if "read_beam" in row:
+        line += "\t%s\t%d\t%.4f" % (row["read_beam"], row["distance_beam"], row["score_beam"])
+    return line
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     from . import net_architecture as NA
     NA.configure(device=torch.device(args.device))
@@ -89,11 +109,12 @@ def main(argv=None):
     save_grid(np.stack(rows), args.out)
     print("wrote %s: %d rows (%d words x %d styles)" % (args.out, len(rows), len(args.words), len(style)))
     if args.read_back:
+        from .evaluate import beam_keywords
         from .legibility import read_back
         R = (NA.make_my_recognizer if args.my_rec else NA.make_recognizer)(in_dim, None, len(CHAR_VEC) + 1, vis_model=False)
         R.load_weights(args.recognizer_weights)
-        for r in read_back(G, R, style[:1], args.words, CHAR_VEC):
-            print("%s\t%s\t%d" % (r["target"], r["read"], r["distance"]))
+        for r in read_back(G, R, style[:1], args.words, CHAR_VEC, **beam_keywords(args, CHAR_VEC, R.device)):
+            print(format_read_back(r))
 
 
 if __name__ == "__main__":
